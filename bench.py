@@ -2,6 +2,7 @@
 """Headline benchmark: inception_v3 100-class bf16 TRAIN on synthetic IFCB ROIs (BASELINE.json configs[1]).
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full --dump-outputs DIR
     python bench.py --gpus N --steps K --warmup W          # starts its N ranks itself (self_launch below), or, equivalently,
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
@@ -9,9 +10,14 @@
 One "step" = one pass of the hot path over one per-GPU batch of 256 synthetic ROIs that are already
 resident in HBM as ragged u8 images: on-GPU PIL-exact resize/normalise -> forward -> CE(+0.4 aux) ->
 backward -> (gradient all-reduce over RCCL when N>1, overlapped with backward) -> Adam -> bf16 weight
-repack.  Rank 0 prints ONE JSON line.  ``roofline`` is measured with HIP events recorded around every
-launch of the timed steps themselves (ifcbk_run_program_ev, no extra synchronisation); ``cpu_baseline``
-times the CPU oracle (the reference's torch-CPU arithmetic) on the host cores, rank 0, N=1 only.
+repack.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times --steps steps, writes the last step's outputs if --dump-outputs is
+given, and prints the line.  Everything else it measures runs with --full only: the untimed per-op survey
+pass and the ``roofline`` (HIP events recorded around every launch of the dominant kernel in the timed
+steps themselves, ifcbk_run_program_ev, no extra synchronisation), the inference, PCIe-inclusive, RUN-mode
+and fp32 legs, the N>1 single-GPU step and exposed exchange time, and ``cpu_baseline`` (the CPU oracle,
+the reference's torch-CPU arithmetic, on the host cores, rank 0, N=1 only).
 """
 import argparse
 import ctypes as C
@@ -250,6 +256,30 @@ def lib_sha16():
     return hashlib.sha256(open(_lib.LIB_PATH, 'rb').read()).hexdigest()[:16]
 
 
+DUMP_SAMPLE = 1 << 22           # elements of the weight / gradient samples: 2 x 16 MB of float32
+
+
+def dump_outputs(eng, B, out_dir, seed=4321):
+    """--dump-outputs: what a caller of the timed train step holds after the last timed step, as float32 .npy files -- the loss
+    (CE + 0.4 CE_aux), the logits of every head, the BatchNorm running statistics, and the updated fp32 weights and the step's
+    gradient at a fixed seeded sample of DUMP_SAMPLE flat positions (both in full would be 2 x 109 MB)"""
+    import numpy as np
+    torch.cuda.synchronize()
+    os.makedirs(out_dir, exist_ok=True)
+    n = eng.P.numel()
+    idx = torch.randperm(n, generator=torch.Generator().manual_seed(seed))[:min(DUMP_SAMPLE, n)].sort().values.to(eng.dev)
+    arrs = {'loss': eng.loss, 'bn_running_stats': eng.RB, 'weights_sample': eng.P[idx], 'grads_sample': eng.G[idx]}
+    aux = 0
+    for h in eng.heads:
+        if h.aux:
+            arrs['aux_logits' if aux == 0 else 'aux_logits_%d' % aux] = h.logits[:B]
+            aux += 1
+        else:
+            arrs['logits'] = h.logits[:B]
+    for name, t in arrs.items():
+        np.save(os.path.join(out_dir, name + '.npy'), t.detach().float().cpu().numpy())
+
+
 def stage_of(tag):
     """network stage of an op by its layer tag (the spatial size the layer's convs work at)"""
     t = tag.split('+')[0]
@@ -455,7 +485,17 @@ def main():
     ap.add_argument('--train-only', action='store_true', help='skip the secondary RUN-mode (inference) measurement: '
                     'the process then launches training kernels only, so a rocprofv3 --stats summary of it is comparable '
                     'launch for launch with the per-kernel HIP-event times')
+    ap.add_argument('--full', action='store_true', help='also measure everything beyond the headline: survey pass and roofline, '
+                    'inference, PCIe-inclusive, RUN-mode, fp32 and CPU-baseline legs (N>1: the single-GPU step and the exposed '
+                    'exchange time); --no-events, --dump-ops, --infer-rois, --fp32-steps, --train-only and --no-cpu-baseline '
+                    'shape those legs')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write the outputs of the last timed step (loss, logits, '
+                    'BatchNorm running statistics, seeded samples of the updated weights and the gradient) as DIR/<name>.npy')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
+    if args.dump_ops and not args.full:
+        ap.error('--dump-ops needs --full (the per-op table comes from the survey pass)')
 
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         # started the way the driver starts the N = 1 run, with --gpus N: become the launcher (before any GPU call)
@@ -492,7 +532,7 @@ def main():
     eng.target[:B].copy_(torch.randint(0, args.classes, (B,), generator=torch.Generator().manual_seed(99 + rank)))
     eng.load_rois(**rois)          # (the plan is per input kind: grey ROIs arrive as the resized u8 plane)
     pl = eng.plan(B)
-    do_survey = (not args.no_events) and args.steps <= 256
+    do_survey = args.full and (not args.no_events) and args.steps <= 256
     use_ev = do_survey and world == 1        # events in the timed region: single-GPU runs only (the N>1 step is several programs)
 
     allred, exchange_name = None, None
@@ -533,7 +573,7 @@ def main():
         else:
             eng.load_rois(**rois)
         if world > 1:
-            eng.train_step_ddp(B, world, allred, mark=ex_mark if timing_on[0] else None)
+            eng.train_step_ddp(B, world, allred, mark=ex_mark if timing_on[0] and args.full else None)
         else:
             eng.train_step(B, ev_slot=k, ev_arr=None if ev_arrs is None else ev_arrs[eng.in_slot])
         if pipelined and not stage_first:
@@ -606,7 +646,7 @@ def main():
     # the cost of communication from the cost of the lane change in the first scaling curve.  Every replica is then put back on
     # rank 0's state.
     single_same_lanes_ms = None
-    if world > 1:
+    if world > 1 and args.full:
         for k in range(13):
             if k == 3:
                 torch.cuda.synchronize()
@@ -639,10 +679,13 @@ def main():
         tt = torch.tensor([dt], device=eng.dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
-        exposed_ms = sum(a.elapsed_time(b) for a, b in zip(ex_events[0::2], ex_events[1::2])) / max(1, len(ex_events) // 2)
+        if ex_events:
+            exposed_ms = sum(a.elapsed_time(b) for a, b in zip(ex_events[0::2], ex_events[1::2])) / max(1, len(ex_events) // 2)
         rank_devices = [None] * world
         dist.all_gather_object(rank_devices, int(local))
     loss = float(eng.loss.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, B, args.dump_outputs)
 
     # secondary number (BASELINE metric is "train + infer"): RUN-mode inference on the same ROIs -- on-GPU
     # preprocess -> eval forward (BN from running statistics) -> softmax; replicas only, no collective
@@ -658,29 +701,30 @@ def main():
         if pipelined and not stage_first:
             stage()
 
-    n_inf = 0 if args.train_only else args.steps
-    for _ in range(2 if n_inf else 0):
-        infer_step()
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    ti = time.perf_counter()
-    for _ in range(n_inf):
-        infer_step()
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    dti = time.perf_counter() - ti
-    if world > 1:
-        tt = torch.tensor([dti], device=eng.dev, dtype=torch.float64)
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        dti = float(tt.item())
+    n_inf = args.steps if args.full and not args.train_only else 0
+    if n_inf:
+        for _ in range(2):
+            infer_step()
+        torch.cuda.synchronize()
+        if world > 1:
+            dist.barrier()
+        ti = time.perf_counter()
+        for _ in range(n_inf):
+            infer_step()
+        torch.cuda.synchronize()
+        if world > 1:
+            dist.barrier()
+        dti = time.perf_counter() - ti
+        if world > 1:
+            tt = torch.tensor([dti], device=eng.dev, dtype=torch.float64)
+            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+            dti = float(tt.item())
 
     # PCIe-inclusive rate (the boundary as the product's DataLoader feeds it: a pinned host batch per step -- one ragged u8 blob
     # plus offset / size tables, <= 23 MB): upload -> on-GPU preprocess -> train step, on one stream and with one batch of
     # look-ahead on the side stream (neuston_net.Trainer's loop).  Never the headline `value`.
     pcie = None
-    if world == 1 and not args.train_only:
+    if args.full and world == 1 and not args.train_only:
         hostb = {k: (v.cpu().pin_memory() if torch.is_tensor(v) else v) for k, v in rois.items()}
         up = lambda: {k: (v.to(eng.dev, non_blocking=True) if torch.is_tensor(v) else v) for k, v in hostb.items()}
 
@@ -731,17 +775,17 @@ def main():
                                           'one train step per timed step') if pipelined else 'preprocess then step on one stream'},
             'train_tflops': round(ips * TRAIN_GFLOP_PER_IMG * 1e-3, 2),
             'mfma_frac_whole_step': round(ips * TRAIN_GFLOP_PER_IMG * 1e-3 / (world * MFMA_BF16_PEAK_TFLOPS), 4),
-            'final_loss': round(loss, 4),
+            'final_loss': round(loss, 4), 'full': args.full,
         }
         if world > 1:
             segs = eng.ddp_segments(pl)
             out['exchange'] = {'algorithm': exchange_name, 'backend': dist.get_backend(), 'buckets': len(segs),
                                'bucket_bytes': [int(4 * (sg[3] - sg[2])) for sg in segs],
-                               'exposed_ms_per_step': round(exposed_ms, 4),
+                               'exposed_ms_per_step': None if exposed_ms is None else round(exposed_ms, 4),
                                'note': 'fp32 sum of the flat gradient, one bucket per backward segment, launched behind the segment '
                                        'that completes it; exposed = HIP-event pair around the waits behind the last segment, rank 0, '
-                                       'mean over the timed steps (IFCBK_DP_EXCHANGE=allreduce|rsag)'}
-            out['single_gpu_same_lanes_ms'] = round(single_same_lanes_ms, 3)
+                                       'mean over the timed steps (IFCBK_DP_EXCHANGE=allreduce|rsag; measured with --full)'}
+            out['single_gpu_same_lanes_ms'] = None if single_same_lanes_ms is None else round(single_same_lanes_ms, 3)
             out['single_gpu_same_lanes_note'] = ('rank 0, 10 local train steps (preprocess + fused step, no exchange) at this job\'s %d program '
                                                  'lanes, timed before the DP loop: efficiency of the exchange alone = this / ms_per_step' % eng.NL)
             out['cpu_baseline'] = None
@@ -836,14 +880,17 @@ def main():
                                      ms=ms[j], gflop=fl.value / 1e9, mbytes=by.value / 1e6))
                 with open(args.dump_ops, 'w') as f:
                     json.dump(rows, f)
-        if world == 1 and not args.train_only:
+        if args.full and world == 1 and not args.train_only:
             del eng
             torch.cuda.empty_cache()
             if args.infer_rois > 0:
                 out['run_mode'] = run_mode_leg(args, local)
             if args.fp32_steps > 0:
                 out['fp32_parity_mode'] = fp32_leg(args, local)
-        if world == 1 and not args.no_cpu_baseline:
+        if not args.full and world == 1:
+            out['cpu_baseline'] = None
+            out['cpu_baseline_reason'] = 'measured by a --full run only'
+        elif world == 1 and not args.no_cpu_baseline:
             eng = None
             torch.cuda.empty_cache()
             out['cpu_baseline'] = cpu_baseline()

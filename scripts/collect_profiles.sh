@@ -5,7 +5,7 @@
 set -o pipefail
 R=$(pwd); T=${1:-prof}; O=$R/gpurun_out/$T; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --train-only > $O/bench_train_only_under_rocprof.json 2> $O/stats.err || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --train-only > $O/bench_train_only_under_rocprof.json 2> $O/stats.err || exit 1
 cp $(ls $O/stats/*/*kernel_stats.csv | head -1) $O/kernel_stats.csv
 echo "stats done"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/f -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-events --train-only > $O/f.json 2> $O/f.err || exit 1

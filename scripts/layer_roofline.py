@@ -1,6 +1,6 @@
-"""Per-op roofline table of one training step (SURVEY.md hard-part 1): for every conv launch of `bench.py --dump-ops ops.json`
+"""Per-op roofline table of one training step (SURVEY.md hard-part 1): for every conv launch of `bench.py --full --dump-ops ops.json`
 the achieved TFLOP/s against min(MFMA peak, arithmetic intensity x HBM bandwidth), and the MAC-weighted fractions.
-    python bench.py --dump-ops gpurun_out/ops.json ...;  python scripts/layer_roofline.py gpurun_out/ops.json out.md"""
+    python bench.py --full --dump-ops ops.json ...;  python scripts/layer_roofline.py ops.json out.md"""
 import json
 import sys
 

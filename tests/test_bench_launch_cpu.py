@@ -48,6 +48,20 @@ def test_gpus2_without_launcher_starts_two_ranks_and_relays_one_line(exchange):
     assert out['config']['IFCBK_LANES'] == 2 and out['config']['weight_gradient_lanes'] == 1      # WORLD_SIZE=2 -> the DP default
 
 
+def _cmdlines():
+    """{pid: full command line} of every process we can see, from /proc (`ps` cuts lines to the terminal width, and the
+    repository path inside a rank's command line can be longer than that)"""
+    out = {}
+    for d in os.listdir('/proc'):
+        if d.isdigit():
+            try:
+                with open('/proc/%s/cmdline' % d, 'rb') as f:
+                    out[int(d)] = f.read().replace(b'\0', b' ').decode(errors='replace')
+            except OSError:
+                pass
+    return out
+
+
 def test_the_launcher_takes_its_ranks_with_it_when_it_is_terminated():
     """a driver that kills `bench.py --gpus N` must not leave the N ranks running as orphans"""
     import signal
@@ -58,9 +72,7 @@ def test_the_launcher_takes_its_ranks_with_it_when_it_is_terminated():
     t0 = time.time()
     while time.time() - t0 < 120 and len(pids) < 2:          # wait until both ranks exist (children of torch.distributed.run)
         time.sleep(1.0)
-        out = subprocess.run(['ps', '-eo', 'pid,args'], stdout=subprocess.PIPE, text=True).stdout
-        pids = {int(ln.split()[0]) for ln in out.splitlines() if BENCH in ln and 'torch.distributed.run' not in ln
-                and int(ln.split()[0]) != p.pid}
+        pids = {q for q, args in _cmdlines().items() if BENCH in args and 'torch.distributed.run' not in args and q != p.pid}
     assert len(pids) >= 2, 'the ranks never started'
     p.send_signal(signal.SIGTERM)
     p.wait(timeout=60)
