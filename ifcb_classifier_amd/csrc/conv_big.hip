@@ -368,8 +368,7 @@ void launch_big(const ConvArgs& a, hipStream_t st) {
         hipLaunchKernelGGL((conv_pp2<TN, MT, PM0, 4>), grid, block, 0, st, a);
         return;
     }
-    if (a.bs_tab) hipLaunchKernelGGL((conv_pp2<TN, MT, PM0, 5>), grid, block, 0, st, a);
-    else if (a.bs_raw) hipLaunchKernelGGL((conv_pp2<TN, MT, PM0, 3>), grid, block, 0, st, a);
+    if (a.bs_raw) hipLaunchKernelGGL((conv_pp2<TN, MT, PM0, 3>), grid, block, 0, st, a);
     else hipLaunchKernelGGL((conv_pp2<TN, MT, PM0, 0>), grid, block, 0, st, a);
 }
 

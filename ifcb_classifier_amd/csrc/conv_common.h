@@ -20,10 +20,7 @@ struct ConvArgs {
     const void* bs_raw;
     const float *bs_mean, *bs_invstd, *bs_scale, *bs_shift;
     int bs_ld;
-    // ... or, when the output gradient belongs to a CONCATENATION of several producers (an Inception block output consumed by the
-    // next block's sibling GEMM): one entry per 8 output channels with that chunk's producer (raw tensor, statistics); raw == null:
-    // the chunk has no BatchNorm producer (a pooled slice).  Sums land in part[mblock][2][K] at the chunk's own columns.
-    const ifcbk_bs_chunk* bs_tab;
+    const void* pad_;          // unused: keeps the offsets (and so the scalar argument loads) of the fields below
     unsigned xbytes, wbytes;   // buffer-descriptor extents of x and w
     int H, W, C, ldx;
     int K, R, S;
@@ -98,8 +95,7 @@ __device__ __forceinline__ void wait_vmcnt() {
 template <class T, int BM, int BN, int NTHREADS, int MODE>
 __device__ __forceinline__ void conv_epilogue_store(const ConvArgs& a, T* sC, float* sRed, const int t, const int lane, const int wave,
                                                     const int m0, const int n0, const int mtile) {
-    constexpr bool BSTAT = MODE == 3 || MODE == 5;        // 3: one producer (a.bs_raw ...), 5: per-chunk producer table (a.bs_tab)
-    constexpr bool BTAB = MODE == 5;
+    constexpr bool BSTAT = MODE == 3;        // one producer (a.bs_raw ...)
     constexpr int ES = (int)sizeof(T);
     constexpr int CE = 16 / ES;
     constexpr int NW = NTHREADS / 64;
@@ -118,29 +114,13 @@ __device__ __forceinline__ void conv_epilogue_store(const ConvArgs& a, T* sC, fl
         if (cvalid) {
             const int nn = n0 + cc * CE;
             float bmu[CE], bis[CE], bsc[CE], bsh[CE];
-            const T* braw = nullptr;                 // this thread's chunk of the producing BatchNorm's input, pixel 0
-            int bld = 0;
             if (BSTAT) {
-                if (BTAB) {
-                    const ifcbk_bs_chunk e = a.bs_tab[nn >> 3];
-                    const int off = nn & 7;
-                    braw = e.raw ? (const T*)e.raw + off : nullptr;
-                    bld = e.raw_ld;
 #pragma unroll
-                    for (int j = 0; j < CE; ++j) {
-                        bmu[j] = braw ? e.stat[off + j] : 0.f;
-                        bis[j] = braw ? e.stat[e.stat_ld + off + j] : 0.f;
-                        bsc[j] = braw ? e.stat[2 * e.stat_ld + off + j] : 0.f;
-                        bsh[j] = braw ? e.stat[3 * e.stat_ld + off + j] : 0.f;
-                    }
-                } else {
-#pragma unroll
-                    for (int j = 0; j < CE; ++j) {
-                        bmu[j] = a.bs_mean[nn + j];
-                        bis[j] = a.bs_invstd[nn + j];
-                        bsc[j] = a.bs_scale[nn + j];
-                        bsh[j] = a.bs_shift[nn + j];
-                    }
+                for (int j = 0; j < CE; ++j) {
+                    bmu[j] = a.bs_mean[nn + j];
+                    bis[j] = a.bs_invstd[nn + j];
+                    bsc[j] = a.bs_scale[nn + j];
+                    bsh[j] = a.bs_shift[nn + j];
                 }
             }
             float sc[CE], sh[CE];
@@ -168,10 +148,9 @@ __device__ __forceinline__ void conv_epilogue_store(const ConvArgs& a, T* sC, fl
             // whole batch are requested before the first is used -- one exposed memory latency per batch instead of per row
             // (an accumulating 1x1 dgrad into a 288-channel block input ran at 1.5 TB/s with a load -> wait -> store loop)
             constexpr int RT = BM / RPP;
-            // MODE 3 keeps batches of four raw rows (eight cost conv_igemm<5,..,3> its second resident block: 71 -> 125 us on the 8x8
-            // layers); the table form (one block per CU on the wide tiles, nothing to lose) takes eight where the rows divide
-            // (narrow tiles, <= 96 channels, gain from eight: 35x35 dgrads 0.113 -> 0.099 ms)
-            constexpr int UB = BTAB ? (RT % 8 == 0 ? 8 : 4) : BSTAT ? ((RT % 8 == 0 && BN <= 96) ? 8 : 4) : (RT < 8 ? RT : 8);
+            // MODE 3 keeps batches of four raw rows on the wide tiles (eight cost conv_igemm<5,..,3> its second resident block: 71 ->
+            // 125 us on the 8x8 layers) and takes eight where the rows divide on narrow tiles (<= 96 channels)
+            constexpr int UB = BSTAT ? ((RT % 8 == 0 && BN <= 96) ? 8 : 4) : (RT < 8 ? RT : 8);
             for (int b = 0; b < RT; b += UB) {
                 typename Chunk<T>::raw_t pre[UB], prer[UB], prb[UB];
                 size_t opx[UB];
@@ -197,11 +176,7 @@ __device__ __forceinline__ void conv_epilogue_store(const ConvArgs& a, T* sC, fl
                     if (m < a.M) {
                         if (a.accumulate) pre[u] = Chunk<T>::load_raw((const T*)a.y + opx[u] * a.ldy + nn);
                         if (a.ep_scale && a.ep_res) prer[u] = Chunk<T>::load_raw((const T*)a.ep_res + (MODE == 2 ? (size_t)m : opx[u]) * a.ep_ldr + nn);
-                        if (BTAB) {
-                            if (braw) prb[u] = Chunk<T>::load_raw(braw + opx[u] * bld);
-                        } else if (BSTAT) {
-                            prb[u] = Chunk<T>::load_raw((const T*)a.bs_raw + opx[u] * a.bs_ld + nn);
-                        }
+                        if (BSTAT) prb[u] = Chunk<T>::load_raw((const T*)a.bs_raw + opx[u] * a.bs_ld + nn);
                     }
                 }
 #pragma unroll
@@ -215,7 +190,7 @@ __device__ __forceinline__ void conv_epilogue_store(const ConvArgs& a, T* sC, fl
                     T* dst = MODE == 4 ? segbase + opx[u] * segld : (T*)a.y + opx[u] * a.ldy + nn;
                     float fv[CE];
                     if (a.part || a.accumulate || a.ep_scale) Chunk<T>::widen(rawc, fv);
-                    if (BSTAT && (!BTAB || braw)) {
+                    if (BSTAT) {
                         float fx[CE];
                         Chunk<T>::widen(prb[u], fx);
 #pragma unroll

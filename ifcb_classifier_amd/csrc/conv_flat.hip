@@ -474,7 +474,7 @@ int ifcbk_conv_flat_rows(int dtype, int N, int H, int W, int cin, int kout, int 
     return flat_grid(nseg);
 }
 
-// (the caller has checked ifcbk_conv_flat_rows; accumulate / residual / segmented / table forms stay with the implicit GEMM)
+// (the caller has checked ifcbk_conv_flat_rows; accumulate / residual / segmented forms stay with the implicit GEMM)
 int ifcbk_conv_flat_launch(ifcbk_ctx* ctx, void* args, int N, hipStream_t st) {
     ConvArgs& a = *reinterpret_cast<ConvArgs*>(args);
     FlatArgs f;

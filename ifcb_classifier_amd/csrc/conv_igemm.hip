@@ -108,7 +108,7 @@ __global__ __launch_bounds__(128 * WM) void conv_igemm(ConvArgs a) {
 
     // 1x1 filter without padding (most layers of the inception / resnet graphs): the gather is a plain row read --
     // per-lane offsets are constants and the k advance is a scalar (soffset): no per-step VALU address work at all
-    const bool plain = (MODE == 0 || MODE == 3 || MODE == 4 || MODE == 5) && a.R == 1 && a.S == 1 && a.base_h == 0 && a.base_w == 0;
+    const bool plain = (MODE == 0 || MODE == 3 || MODE == 4) && a.R == 1 && a.S == 1 && a.base_h == 0 && a.base_w == 0;
     unsigned va[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) va[j] = bh[j] >= 0 ? (unsigned)(off0[j] + csrc * CE) * (unsigned)ES : OOB;
@@ -460,21 +460,16 @@ __global__ __launch_bounds__(512) void conv_ws(ConvArgs a, int total_tiles) {
 }
 
 // N-tile choice.  Per-block time ~ (BN + 48) (measured round 1: the 48 stands for the pixel tile's load + the fixed parts),
-// so without other constraints the widest tile that wastes no columns wins.  IFCBK_CONV_MQ=1 also counts ROUNDS: the chip
-// holds 512 blocks (2 per CU); a 578-block grid (every 17x17 layer with K <= 192 at batch 256) runs a second, nearly empty
-// round, and narrower tiles (more, shorter blocks) can finish sooner.
-int pick_nt(int K, int maxnt, int M, int bm) {
-    static int force = -1, mq = -1;
+// so without other constraints the widest tile that wastes no columns wins.
+int pick_nt(int K, int maxnt) {
+    static int force = -1;
     if (force < 0) { const char* e = getenv("IFCBK_CONV_NT"); force = e ? atoi(e) : 0; }
-    if (mq < 0) { const char* e = getenv("IFCBK_CONV_MQ"); mq = e ? atoi(e) : 0; }
     if (force > 0 && force <= maxnt) return force;
     int best = 1;
     long bestc = -1;
-    const long tilesM = M > 0 && mq ? cdiv(M, bm) : 0;
     for (int nt = 1; nt <= maxnt; ++nt) {
         int bn = 32 * nt;
         long c = (long)cdiv(K, bn) * (bn + 48);
-        if (tilesM) c = cdiv(tilesM * cdiv(K, bn), 512) * (bn + 48);
         if (bestc < 0 || c < bestc || (c == bestc && nt > best)) { bestc = c; best = nt; }
     }
     return best;
@@ -511,7 +506,6 @@ void launch(const ConvArgs& a, hipStream_t st) {
     int tilesM = cdiv(a.M, 64 * WM);
     dim3 grid((unsigned)(tilesM * a.tilesN)), block(128 * WM);
     if (a.seg_n) hipLaunchKernelGGL((conv_igemm<T, NT, WM, NSTAGE, 4>), grid, block, 0, st, a);
-    else if (a.bs_tab) hipLaunchKernelGGL((conv_igemm<T, NT, WM, NSTAGE, 5>), grid, block, 0, st, a);
     else if (a.bs_raw) hipLaunchKernelGGL((conv_igemm<T, NT, WM, NSTAGE, 3>), grid, block, 0, st, a);
     else if (a.wKg) hipLaunchKernelGGL((conv_igemm<T, NT, WM, NSTAGE, 2>), grid, block, 0, st, a);
     else if (a.ish | a.isw) hipLaunchKernelGGL((conv_igemm<T, NT, WM, NSTAGE, 1>), grid, block, 0, st, a);
@@ -538,7 +532,7 @@ int ws_max_tiles() {
 bool ws_shape_ok(int dtype, int M, int K, int Kg) {
     const int ms = ws_min_steps();
     if (ms <= 0 || dtype != IFCBK_BF16 || pick_wm(M, K) != 2 || cdiv(Kg, 64) < ms) return false;
-    const int nt = pick_nt(K, 6, M, 128);
+    const int nt = pick_nt(K, 6);
     return (int64_t)cdiv(M, 128) * cdiv(K, 32 * nt) <= ws_max_tiles();
 }
 int num_cus() {
@@ -562,21 +556,21 @@ void launch_ws(const ConvArgs& a, hipStream_t st) {
 // the wide-tile kernel serves plain gathers (forward of any stride, stride-1 input gradients), with every epilogue variant
 bool big_ok(const ConvArgs& a) { return !a.wKg && !(a.ish | a.isw); }
 bool pp3_ok(const ConvArgs& a) {
-    return big_ok(a) && !a.seg_n && !a.bs_raw && !a.bs_tab && !a.accumulate && !a.ep_res && (a.ep_scale == nullptr || a.part == nullptr);
+    return big_ok(a) && !a.seg_n && !a.bs_raw && !a.accumulate && !a.ep_res && (a.ep_scale == nullptr || a.part == nullptr);
 }
 
 int run(ifcbk_ctx* ctx, ConvArgs& a, int dtype, hipStream_t st) {
     const bool f32 = dtype == IFCBK_F32;
-    if (!a.wKg && !(a.ish | a.isw) && a.ostr_h == 1 && a.ostr_w == 1 && !a.seg_n && !a.bs_tab && !a.accumulate && !a.ep_res && a.PQ > 0) {
+    if (!a.wKg && !(a.ish | a.isw) && a.ostr_h == 1 && a.ostr_w == 1 && !a.seg_n && !a.accumulate && !a.ep_res && a.PQ > 0) {
         // stride-1 3x3 / 5x5 layers over 48..96 channels: the flat-image kernel (conv_flat.hip)
         const int N = a.M / a.PQ;
         if (ifcbk_conv_flat_rows(dtype, N, a.H, a.W, a.C, a.K, a.R, a.S, -a.base_h, -a.base_w, a.P, a.Q) > 0)
             return ifcbk_conv_flat_launch(ctx, &a, N, st);
     }
-    // stride-1 multi-tap layers of the 17x17 class: the pixel-slab kernel (conv_slab.hip); every epilogue but the table / segment forms.
+    // stride-1 multi-tap layers of the 17x17 class: the pixel-slab kernel (conv_slab.hip); every epilogue but the segment form.
     // Its reduction order differs from the other kernels' (same products, fp32 sums in another order), so the plan looks at the layer's
     // shape only: whatever the batch, such a layer always takes this kernel, and an eval batch equals its parts bit for bit
-    if (big_ok(a) && a.ostr_h == 1 && a.ostr_w == 1 && !a.seg_n && !a.bs_tab && a.PQ > 0) {
+    if (big_ok(a) && a.ostr_h == 1 && a.ostr_w == 1 && !a.seg_n && a.PQ > 0) {
         const int N = a.M / a.PQ;
         if (ifcbk_conv_slab_plan(dtype, N, a.H, a.W, a.C, a.K, a.R, a.S, -a.base_h, -a.base_w, a.P, a.Q) > 0)
             return ifcbk_conv_slab_launch(ctx, &a, N, st);
@@ -588,7 +582,7 @@ int run(ifcbk_ctx* ctx, ConvArgs& a, int dtype, hipStream_t st) {
         if (big_ok(a) && ifcbk_conv_big_plan(dtype, a.M, a.K, a.Kg, &bmt, &btn)) return ifcbk_conv_big_launch(ctx, &a, bmt, btn, st);
     }
     int wm = f32 ? 2 : pick_wm(a.M, a.K);
-    int nt = pick_nt(a.K, f32 ? 4 : (wm == 4 ? 5 : 6), a.M, 64 * wm);
+    int nt = pick_nt(a.K, f32 ? 4 : (wm == 4 ? 5 : 6));
     a.tilesN = cdiv(a.K, 32 * nt);
     if ((int64_t)cdiv(a.M, 64 * wm) * a.tilesN >= (1ll << 31)) IFCBK_FAIL(ctx, IFCBK_EINVAL, "conv: grid too large");
     if (ws_shape_ok(dtype, a.M, a.K, a.Kg) && !a.seg_n && !a.bs_raw && !a.wKg && !(a.ish | a.isw) && !a.accumulate && !a.ep_res) {
@@ -636,7 +630,7 @@ int run(ifcbk_ctx* ctx, ConvArgs& a, int dtype, hipStream_t st) {
 
 int ifcbk_num_cus() { return num_cus(); }
 
-int ifcbk_conv_fwd_nt(int K, int M) { return pick_nt(K, pick_wm(M, K) == 4 ? 5 : 6, M, 64 * pick_wm(M, K)); }
+int ifcbk_conv_fwd_nt(int K, int M) { return pick_nt(K, pick_wm(M, K) == 4 ? 5 : 6); }
 
 int ifcbk_conv_fwd_wm(int M, int K) { return pick_wm(M, K); }
 
@@ -771,7 +765,7 @@ static int conv_fwd_impl(ifcbk_ctx* ctx, const ifcbk_conv_desc* d, const void* x
     a.dbg = 0; a.tr = 0; a.fP = make_fastdiv(1);
     a.ep_scale = scale; a.ep_shift = shift; a.ep_res = residual; a.ep_ldr = ldr; a.ep_relu = relu;
     a.x = x; a.w = w; a.y = y; a.part = bn_part;
-    a.bs_raw = nullptr; a.bs_mean = a.bs_invstd = a.bs_scale = a.bs_shift = nullptr; a.bs_ld = 0; a.bs_tab = nullptr;
+    a.bs_raw = nullptr; a.bs_mean = a.bs_invstd = a.bs_scale = a.bs_shift = nullptr; a.bs_ld = 0;
     a.seg_n = seg ? seg->n : 0;
     for (int q = 0; q < 4; ++q) {
         a.seg_end[q] = seg ? seg->end[q] : 0; a.seg_ld[q] = seg ? seg->ld[q] : 0; a.seg_aff[q] = seg ? seg->aff[q] : 0;
@@ -795,7 +789,6 @@ struct BnStatArgs {
     int ld;
     const float *mean, *invstd, *scale, *shift;
     float* part;
-    const ifcbk_bs_chunk* tab;
 };
 
 // the fused variant exists for the plain (stride-1, first-writer, implicit-GEMM) input gradient only
@@ -830,16 +823,7 @@ extern "C" int ifcbk_conv2d_dgrad_bnstat(ifcbk_ctx* ctx, const ifcbk_conv_desc* 
     if (!d || !dgrad_bnstat_ok(d)) IFCBK_FAIL(ctx, IFCBK_EUNSUPPORTED, "conv2d_dgrad_bnstat: stride-1 implicit-GEMM input gradients only");
     if (!prev_raw || !prev_mean || !prev_invstd || !prev_scale || !prev_shift || !part)
         IFCBK_FAIL(ctx, IFCBK_EINVAL, "conv2d_dgrad_bnstat: null operand");
-    BnStatArgs bs = {prev_raw, prev_ld, prev_mean, prev_invstd, prev_scale, prev_shift, part, nullptr};
-    return dgrad_impl(ctx, d, dy, wT, dx, 0, &bs, stream);
-}
-
-extern "C" int ifcbk_conv2d_dgrad_bnstat_table(ifcbk_ctx* ctx, const ifcbk_conv_desc* d, const void* dy, const void* wT, void* dx,
-                                               const ifcbk_bs_chunk* table, float* part, void* stream) {
-    if (!d || !dgrad_bnstat_ok(d)) IFCBK_FAIL(ctx, IFCBK_EUNSUPPORTED, "conv2d_dgrad_bnstat_table: stride-1 implicit-GEMM input gradients only");
-    if (!table || !part) IFCBK_FAIL(ctx, IFCBK_EINVAL, "conv2d_dgrad_bnstat_table: null operand");
-    if (d->C % 8) IFCBK_FAIL(ctx, IFCBK_EINVAL, "conv2d_dgrad_bnstat_table: C must be a multiple of 8");
-    BnStatArgs bs = {table, 0, nullptr, nullptr, nullptr, nullptr, part, table};       // raw != null selects MODE 3
+    BnStatArgs bs = {prev_raw, prev_ld, prev_mean, prev_invstd, prev_scale, prev_shift, part};
     return dgrad_impl(ctx, d, dy, wT, dx, 0, &bs, stream);
 }
 
@@ -856,7 +840,7 @@ static int dgrad_impl(ifcbk_ctx* ctx, const ifcbk_conv_desc* d, const void* dy, 
     a.ep_scale = nullptr; a.ep_shift = nullptr; a.ep_res = nullptr; a.ep_ldr = 0; a.ep_relu = 0;
     a.x = dy; a.w = wT; a.y = dx; a.part = bs ? bs->part : nullptr;
     a.seg_n = 0;
-    a.bs_raw = bs ? bs->raw : nullptr; a.bs_ld = bs ? bs->ld : 0; a.bs_tab = bs ? bs->tab : nullptr;
+    a.bs_raw = bs ? bs->raw : nullptr; a.bs_ld = bs ? bs->ld : 0;
     a.bs_mean = bs ? bs->mean : nullptr; a.bs_invstd = bs ? bs->invstd : nullptr;
     a.bs_scale = bs ? bs->scale : nullptr; a.bs_shift = bs ? bs->shift : nullptr;
     const int es = dtype_esize(d->dtype);

@@ -15,10 +15,12 @@ from . import _lib
 from ._lib import Op, ConvDesc, BnDesc, PoolDesc, HeadDesc, RoiDesc
 
 
-# environment switches the library's conv dispatch reads per launch (csrc/conv_igemm.hip, conv_big.hip, conv_flat.hip, conv_wgrad*.hip)
-_DISPATCH_SWITCHES = ('IFCBK_FWD_LANES', 'IFCBK_CONV_PP3', 'IFCBK_CONV_PP3_GRID', 'IFCBK_WGRAD_LANE', 'IFCBK_WGRAD_GROUP', 'IFCBK_WGRAD_GROUP_MINKH', 'IFCBK_CONV_BIG', 'IFCBK_CONV_SLAB', 'IFCBK_CONV_BIG_MT', 'IFCBK_CONV_BIG_TN', 'IFCBK_CONV_FLAT', 'IFCBK_CONV_NT',
-                      'IFCBK_CONV_WM', 'IFCBK_CONV_MQ', 'IFCBK_CONV_WS', 'IFCBK_CONV_WS_TILES', 'IFCBK_CONV_ROWS', 'IFCBK_WGRAD_PP',
-                      'IFCBK_WGRAD_PP_KH', 'IFCBK_WGRAD_COLS', 'IFCBK_WGRAD_STEM', 'IFCBK_WGRAD_ROUNDS')
+# environment switches the library reads at launch time that change a workspace size or a partial-row count (csrc/conv_*.hip,
+# bn.hip), plus the engine's weight-gradient switches; tests/test_switches_cpu.py checks the list against the library sources
+_DISPATCH_SWITCHES = ('IFCBK_CONV_PP3', 'IFCBK_CONV_PP3_GRID', 'IFCBK_WGRAD_LANE', 'IFCBK_WGRAD_GROUP', 'IFCBK_WGRAD_GROUP_MINKH', 'IFCBK_CONV_BIG', 'IFCBK_CONV_SLAB', 'IFCBK_CONV_BIG_MT', 'IFCBK_CONV_BIG_TN', 'IFCBK_CONV_FLAT', 'IFCBK_CONV_NT',
+                      'IFCBK_CONV_WM', 'IFCBK_CONV_WS', 'IFCBK_CONV_WS_TILES', 'IFCBK_CONV_ROWS', 'IFCBK_WGRAD_PP',
+                      'IFCBK_WGRAD_PP_KH', 'IFCBK_WGRAD_COLS', 'IFCBK_WGRAD_STEM', 'IFCBK_WGRAD_ROUNDS', 'IFCBK_WGRAD_FLAT',
+                      'IFCBK_BN_BWD_ROWS')
 
 
 def _dispatch_env():
@@ -521,7 +523,6 @@ class Engine:
         # (any lane count can be captured: ctx.hip records lane-to-lane edges through the origin stream, see run_lanes)
         self.graph_eval = gm not in ('0', 'off', 'none')
         self.graph_train = gm in ('1', 'all', 'train')
-        self.wgrad_side_lane = os.environ.get('IFCBK_WGRAD_SIDE', '0') != '0' and self.NL > 1
         # IFCBK_WGRAD_LANE=1 (round 4): EVERY weight gradient on the last lane, the branch chains on the others, and every layer keeps
         # its d(raw) in a buffer of its own (4.6 GB at batch 256) -- the backward critical path is then BN-backward -> input gradient
         # -> BN-backward ..., and the MFMA-bound weight gradients (6.7 ms of a step when each runs alone) fill in beside the
@@ -531,15 +532,14 @@ class Engine:
         # 2 + 1 lanes 22.34 | FIVE streams (4 + 1, 3 + 2) 27.7, six 31.8: this runtime has four hardware queues per process.
         # Two lanes (the data-parallel default): 2 chains 22.90 | 1 chain + 1 weight-gradient lane 22.52.
         self.wgrad_lane = int(os.environ.get('IFCBK_WGRAD_LANE', '1' if self.NL >= 2 else '0'))       # number of weight-gradient lanes
-        if self.NL - self.wgrad_lane < 1 or self.wgrad_side_lane:
+        if self.NL - self.wgrad_lane < 1:
             self.wgrad_lane = 0
         # (round 4's least-priority stream for that lane -- 0.0-0.1 ms per step -- is gone: round 5)
         if not self.plan_only:
             self.ctx.call('ifcbk_ctx_set_lanes', self.NL)     # one workspace arena per lane in use (was: always 8)
         max_raw = max([n.P * n.Q * n.K for n in self.convs] + [8])
-        # d(raw) scratch: per lane; two per lane when the weight gradient runs on the side lane (it keeps reading one while
-        # the next node's BN backward already fills the other)
-        self.draw = [torch.zeros(Nt * max_raw, dtype=bf, device=dev) for _ in range(self.NL * (2 if self.wgrad_side_lane else 1))]
+        # d(raw) scratch: per lane
+        self.draw = [torch.zeros(Nt * max_raw, dtype=bf, device=dev) for _ in range(self.NL)]
         gmax = max([g.x.H * g.x.W * g.Ktot for g in self.groups] + [0])
         self.draw_group = torch.zeros(max(1, Nt * gmax), dtype=bf, device=dev)
         mb = max([self.ctx.lib.ifcbk_conv2d_fwd_mblocks(C.byref(self._conv_desc(n, N))) * 2 * n.K for n in self.convs] +
@@ -707,38 +707,6 @@ class Engine:
         """a commuted pool branch's unpooled 1x1-conv output: its channel slice of the sibling GEMM's merged tensor"""
         return _vp(n.group.raw, self.esize * n.koff), n.group.Ktot
 
-    def _bs_table(self, grp, gd, readers, fused_pool):
-        """per-chunk producer table (ifcbk_bs_chunk) of the block input a sibling GEMM reads, when that GEMM is the input's only
-        consumer and every conv that wrote a slice of it is a plain conv -> BN -> ReLU; None otherwise"""
-        import numpy as np
-        x = grp.x
-        members = set(grp.members)
-        for r in readers.get(x.buf.id, ()):
-            if r not in members and not any(m.cpool is r for m in grp.members):
-                return None
-        prods = [m for m in self.net.nodes if m.kind != 'head' and m.y.buf.id == x.buf.id]
-        convs = [m for m in prods if m.kind == 'conv']
-        if not convs or not x.is_full:
-            return None
-        for m in convs:
-            if not m.relu or m.residual is not None or m in fused_pool or m.aux:
-                return None
-        nrow = self.ctx.lib.ifcbk_conv2d_dgrad_bnstat_mblocks(C.byref(gd))
-        if nrow <= 0:
-            return None
-        nchunk = x.C // 8
-        tab = (_lib.BsChunk * nchunk)()
-        for m in convs:
-            rawp, rawld = self._raw_ptr(m)
-            for k in range(m.K // 8):
-                e = tab[m.y.coff // 8 + k]
-                e.raw = rawp.value + k * 8 * self.esize
-                e.stat = self.stats.data_ptr() + 4 * (m.st_off + k * 8)
-                e.raw_ld, e.stat_ld = rawld, m.st_ld
-        table = torch.from_numpy(np.frombuffer(bytes(tab), dtype=np.uint8).copy()).to(self.dev)
-        part = torch.zeros(nrow * 2 * x.C, dtype=torch.float32, device=self.dev)
-        return table, part, nrow, convs
-
     # ------------------------------------------------------------------ programs
     def plan(self, N):
         if N > self.max_batch:
@@ -798,12 +766,12 @@ class Engine:
         # conv c whose input is the private BN+ReLU activation of conv n: c's input-gradient kernel also reduces n's BN
         # backward sums in its epilogue (ifcbk_conv2d_dgrad_bnstat) and n's BN backward skips its reduction pass
         bnstat_of = {}        # consumer conv -> producer conv
-        # 0 off, 1 one-producer layers, 2 + block outputs through a chunk table.  Level 2 is correct (tests run it) but measured
-        # SLOWER at batch 256 (the wide-tile dgrads run one block per CU, nothing hides their epilogue): default 1
-        fuse_level = int(os.environ.get('IFCBK_FUSE_BNSTAT', '1'))
-        fuse_bnstat = fuse_level >= 1
-        keep = []             # device tables / buffers the op tables point into
-        if fuse_bnstat:
+        # IFCBK_FUSE_BNSTAT: 1 (default) fuses, 0 is the unfused reference the parity tests compare against
+        fuse_bnstat = os.environ.get('IFCBK_FUSE_BNSTAT', '1')
+        if fuse_bnstat not in ('0', '1'):
+            raise ValueError('IFCBK_FUSE_BNSTAT must be 0 or 1, got %r' % fuse_bnstat)
+        keep = []             # host tables the op tables point into
+        if fuse_bnstat == '1':
             for cnode in net.nodes:
                 if cnode.kind != 'conv' or cnode.group is not None or cnode.x.buf.is_input or not cnode.x.is_full:
                     continue
@@ -815,7 +783,7 @@ class Engine:
                         and self._conv_desc(cnode, N).C == cnode.x.C      # not the flattened full-cover form: its 'channels' are (tap, c)
                         and self.ctx.lib.ifcbk_conv2d_dgrad_bnstat_mblocks(C.byref(self._conv_desc(cnode, N))) > 0):
                     bnstat_of[cnode] = prod[0]
-        bnstat_done = {}      # producer conv -> (partials pointer, row count, lane of the partial buffer)
+        bnstat_done = {}      # producer conv -> (partials pointer, row count, resource of the partial buffer)
 
         # ---- lanes: every chain of nodes that hangs off a shared tensor (an Inception block input, a resnet block
         # input) gets a lane, round-robin; a node fed by a private tensor stays on its producer's lane
@@ -871,24 +839,6 @@ class Engine:
         WLs = list(range(NL - self.wgrad_lane, NL))        # the weight-gradient lanes
         wl_next = [0]
         lane_of = assign_lanes(NL - self.wgrad_lane)
-        # The TRUNK: the single-chain prefix of the network (inception's stem Conv2d_1a .. 4a + its pools).  Its backward is the end
-        # of the step -- one chain lane busy, the other chain lanes idle -- and its weight gradients (1.0 ms of kernels when each
-        # runs alone) used to queue up on the one weight-gradient lane behind each other.  Round 5: they go round-robin over ALL
-        # lanes but the trunk's own, so that the weight gradients of 4a / 2b / 2a overlap each other beside the trunk's chain
-        # (IFCBK_WGRAD_SPREAD=1; measured on one box, three interleaved rounds: 21.44 vs 21.45 ms per step -- no gain: those kernels cost the step their CU-time, not their queueing -- so the default stays 0: one weight-gradient lane for everything, as in round 4)
-        trunk = set()
-        if self.wgrad_lane and NL - self.wgrad_lane >= 2 and os.environ.get('IFCBK_WGRAD_SPREAD', '0') != '0':
-            body = [m for m in net.nodes if not m.aux and m.kind != 'head']
-            if body:
-                for m in body:
-                    if lane_of[m] != lane_of[body[0]]:
-                        break
-                    trunk.add(m)
-        TLs = [l for l in range(NL - 1, -1, -1) if not trunk or l != lane_of[next(iter(trunk))]] if trunk else []
-        tl_next = [0]
-        # the forward has no weight gradients: IFCBK_FWD_LANES lets its branches use the weight-gradient lane(s) too
-        fwd_lanes = max(1, min(NL, int(os.environ.get('IFCBK_FWD_LANES', str(NL - self.wgrad_lane)))))
-        lane_fwd = assign_lanes(fwd_lanes) if fwd_lanes != NL - self.wgrad_lane else lane_of
         lane_eval = assign_lanes(self.NL_eval)
         if not hasattr(self, 'draw_own'):
             self.draw_own = {}
@@ -953,7 +903,7 @@ class Engine:
         bwd_groups = []
         for k, n in enumerate(net.nodes):
             grp = OpList()
-            L = lane_fwd[n]
+            L = lane_of[n]
             if n.kind == 'conv':
                 M = N * n.P * n.Q
                 d = self._conv_desc(n, N)
@@ -1053,7 +1003,7 @@ class Engine:
                             mbnd = BnDesc(M, m.K, mld, m.y.buf.C, 1, self.cdtype, m.eps, 0.1)
                             if m.cpool is not None:
                                 # commuted pool branch: pool the conv's slice of the merged tensor, then BatchNorm the pooled tensor
-                                Lm, pn = lane_fwd[m], m.cpool
+                                Lm, pn = lane_of[m], m.cpool
                                 pre, ldpre = self._pre_ptr(m)
                                 ppd = PoolDesc(N, pn.x.H, pn.x.W, m.K, ldpre, 3, 3, 1, 1, 1, 1, pn.P, pn.Q, mld, self.cdtype)
                                 rpre, rr2 = ('gr', id(g), m.koff, m.koff + m.K), ('r', m.raw.id, 0, m.K)
@@ -1076,10 +1026,10 @@ class Engine:
                                     p=(_vp(self.bn_part[0], 4 * m.koff), self._pptr(mbk + '.weight'), self._pptr(mbk + '.bias'),
                                        _vp(self.bviews[mbk + '.running_mean']), _vp(self.bviews[mbk + '.running_var']),
                                        self._stat(m, 0), self._stat(m, 1), self._stat(m, 2), self._stat(m, 3)),
-                                    i=(gmb, g.Ktot), bn=mbnd, lane=lane_fwd[m], reads=[rbp(0)], writes=[rst(m)])
+                                    i=(gmb, g.Ktot), bn=mbnd, lane=lane_of[m], reads=[rbp(0)], writes=[rst(m)])
                             lst.add(_lib.OP_BN_APPLY, m.name,
                                     p=(mraw, self._stat(m, 2), self._stat(m, 3), None, self._aptr(m.y)), i=(0,), bn=mbnd,
-                                    lane=lane_fwd[m], reads=[rraw(m), rst(m)], writes=[ra(m.y)])
+                                    lane=lane_of[m], reads=[rraw(m), rst(m)], writes=[ra(m.y)])
                         continue
                     if u8:
                         lst.add(_lib.OP_STEM_U8_FWD, n.name, p=(gu8, self._pptr(ckey), gab, raw, _vp(self.bn_part[L]), None, None),
@@ -1112,11 +1062,9 @@ class Engine:
                 needs_dgrad = not n.x.buf.is_input
                 pack.add(_lib.OP_WEIGHT_PACK, n.name, p=(self._pptr(ckey), wk, wT if needs_dgrad else None), i=(n.wT_ld,), conv=d)
                 # ---- backward of this node
-                di = L * 2 + (k & 1) if self.wgrad_side_lane else L
-                draw = _vp(self.draw[di]) if (g is None or n.cpool is not None) else _vp(self.draw_group, self.esize * n.koff)
-                dres, lddres, dres_acc = None, 0, 0
+                draw = _vp(self.draw[L]) if (g is None or n.cpool is not None) else _vp(self.draw_group, self.esize * n.koff)
                 # (flags resolved later, in reverse order) -> store a closure
-                bwd_groups.append(('conv', n, d, bnd, draw, wT, needs_dgrad, di))
+                bwd_groups.append(('conv', n, d, bnd, draw, wT, needs_dgrad))
             elif n.kind in ('max', 'avg'):
                 pd = PoolDesc(N, n.x.H, n.x.W, n.x.C, n.x.buf.C, n.R, n.S, n.sh, n.sw, n.ph, n.pw, n.P, n.Q, n.y.buf.C,
                               self.cdtype)
@@ -1208,7 +1156,7 @@ class Engine:
         # n times the K-steps per block.  Each member keeps its d(raw) in a buffer of its own until the group has run (the per-lane
         # scratch is reused by the next layer's BatchNorm backward).  IFCBK_WGRAD_GROUP=0 switches it off.
         wg_of, wg_groups = {}, []
-        if os.environ.get('IFCBK_WGRAD_GROUP', '1') != '0' and self.dtype == 'bf16' and not self.wgrad_side_lane:
+        if os.environ.get('IFCBK_WGRAD_GROUP', '1') != '0' and self.dtype == 'bf16':
             buckets = {}
             for gsp in reversed(bwd_groups):
                 if gsp[0] != 'conv':
@@ -1316,18 +1264,15 @@ class Engine:
                     bwd.add(_lib.OP_AVGPOOL_BWD, n.name, p=(self._aptr(n.y, True), self._aptr(n.x, True)), flags=acc, pool=pd,
                             lane=lane_of[n], reads=[rg(n.y)], writes=[rg(n.x)])
             else:
-                _, n, d, bnd, draw, wT, needs_dgrad, di = g
+                _, n, d, bnd, draw, wT, needs_dgrad = g
                 wgq = wg_of.get(n)
                 own = wgq is not None or (self.wgrad_lane and (n.group is None or n.cpool is not None))
                 if own:
-                    draw = _vp(own_draw(n))               # kept until the (grouped / side-lane) weight gradient has read it
+                    draw = _vp(own_draw(n))               # kept until the (grouped / lane's) weight gradient has read it
                 elif self.wgrad_lane:
                     draw = _vp(group_draw(n.group), self.esize * n.koff)
                 LW = None                                 # lane of this node's weight gradient (None: the node's own lane)
-                if self.wgrad_lane and n in trunk:
-                    LW = TLs[tl_next[0] % len(TLs)]       # (the trunk's weight gradients: every lane but the trunk's own)
-                    tl_next[0] += 1
-                elif self.wgrad_lane:
+                if self.wgrad_lane:
                     LW = WLs[wl_next[0] % len(WLs)]       # (round-robin over the weight-gradient lanes, per NODE)
                     wl_next[0] += 1
                 ckey, bkey = n.conv_key + '.weight', n.bn_key
@@ -1339,7 +1284,7 @@ class Engine:
                 grp = n.group
                 L = lane_of[n]
                 cp = n.cpool is not None
-                rdraw = [rdg(n)] if (grp is not None and not cp) else [('draw', di, 0, 1)]     # d(raw): merged-group slice or the lane's scratch
+                rdraw = [rdg(n)] if (grp is not None and not cp) else [('draw', L, 0, 1)]     # d(raw): merged-group slice or the lane's scratch
                 if own:
                     rdraw = [('drawn', id(n), 0, 1)]
                 rawp, _ld = self._raw_ptr(n)
@@ -1352,12 +1297,12 @@ class Engine:
                                self._pptr(bkey + '.weight', 'G'), self._pptr(bkey + '.bias', 'G')),
                             i=(1, n.K), pool=ppd, lane=L, reads=[rraw(n), rg(pn.y), ram(pk), rst(n)], writes=rdraw)
                 elif n in bnstat_done:
-                    ppart, nrow, pres, pld = bnstat_done[n]
+                    ppart, nrow, pres = bnstat_done[n]
                     bwd.add(_lib.OP_BN_BWD_PARTIALS, n.name,
                             p=(rawp, self._aptr(n.y, True), self._pptr(bkey + '.weight'), self._stat(n, 0), self._stat(n, 1),
                                self._stat(n, 2), self._stat(n, 3), ppart, draw, self._pptr(bkey + '.weight', 'G'),
                                self._pptr(bkey + '.bias', 'G')),
-                            i=(n.y.buf.C, nrow, n.K if (grp is None or cp) else grp.Ktot, pld), bn=bnd, lane=L,
+                            i=(n.y.buf.C, nrow, n.K if (grp is None or cp) else grp.Ktot, 0), bn=bnd, lane=L,
                             reads=[rraw(n), rg(n.y), rst(n), pres], writes=rdraw)
                 else:
                     bwd.add(_lib.OP_BN_BWD, n.name,
@@ -1387,29 +1332,12 @@ class Engine:
                                 p=[self._aptr(grp.x), gp[0]] + gp[1:], i=[m.K for m in grp.members], conv=gd,
                                 lane=0 if LW is None else LW, reads=[ra(grp.x), gres], writes=[])
                         acc = acc_flag(grp.x.buf)
-                        tab = self._bs_table(grp, gd, readers, fused_pool) if (acc == 0 and fuse_level >= 2) else None
-                        if tab is not None:
-                            # the sibling GEMM is the ONLY consumer of this block input: its input-gradient kernel is the sole writer
-                            # of the block-output gradient and reduces the BatchNorm-backward sums of every producer of that
-                            # concatenation in its epilogue (per-chunk producer table); the producers skip their reduction pass
-                            table, part, nrow, prods = tab
-                            keep.extend([table, part])
-                            rpt = ('bpt', id(grp), 0, 1)
-                            bwd.add(_lib.OP_CONV_DGRAD_BNSTAT_TAB, '+'.join(m.name for m in grp.members),
-                                    p=(_vp(gdraw), _vp(self.Wsh, self.esize * grp.wT_off), self._aptr(grp.x, True), _vp(table),
-                                       _vp(part)), conv=gd, lane=0,
-                                    reads=[gres] + [rraw(m) for m in prods] + [rst(m) for m in prods], writes=[rg(grp.x), rpt])
-                            for m in prods:
-                                bnstat_done[m] = (_vp(part, 4 * m.y.coff), nrow, rpt, grp.x.C)
-                        else:
-                            bwd.add(_lib.OP_CONV_DGRAD, '+'.join(m.name for m in grp.members),
-                                    p=(_vp(gdraw), _vp(self.Wsh, self.esize * grp.wT_off), self._aptr(grp.x, True)),
-                                    flags=acc, conv=gd, lane=0, reads=[gres], writes=[rg(grp.x)])
+                        bwd.add(_lib.OP_CONV_DGRAD, '+'.join(m.name for m in grp.members),
+                                p=(_vp(gdraw), _vp(self.Wsh, self.esize * grp.wT_off), self._aptr(grp.x, True)),
+                                flags=acc, conv=gd, lane=0, reads=[gres], writes=[rg(grp.x)])
                     continue
                 dbw = ConvDesc.from_buffer_copy(d)
                 dbw.ldy = n.K                       # dy of the conv = the dense d(raw) scratch
-                # wgrad and dgrad only share their input d(raw); IFCBK_WGRAD_SIDE=1 puts the weight gradient on the neighbouring
-                # lane -- measured slower (31.5 vs 29.1 ms/step): the next node's bn_bwd must wait for it to release the scratch
                 if wgq is not None:
                     wgq.setdefault('seen', []).append(n)
                     if len(wgq['seen']) == len(wgq['members']):
@@ -1431,7 +1359,7 @@ class Engine:
                             lane=L if LW is None else LW, reads=[ra(n.x)] + rdraw, writes=[])
                 else:
                     bwd.add(_lib.OP_CONV_WGRAD, n.name, p=(self._aptr(n.x), draw, self._pptr(ckey, 'G')), conv=dbw,
-                            lane=LW if LW is not None else ((L + 1) % NL if self.wgrad_side_lane else L),
+                            lane=L if LW is None else LW,
                             reads=[ra(n.x)] + rdraw, writes=[])
                 if needs_dgrad:
                     assert n.x.is_full
@@ -1444,7 +1372,7 @@ class Engine:
                                 p=(draw, wT, self._aptr(n.x, True), prow, self._stat(pn, 0), self._stat(pn, 1),
                                    self._stat(pn, 2), self._stat(pn, 3), _vp(self.bn_part[L])), i=(pld,), conv=dbw,
                                 lane=L, reads=rdraw + [rraw(pn), rst(pn)], writes=[rg(n.x), rbp(L)])
-                        bnstat_done[pn] = (_vp(self.bn_part[L]), nrow, rbp(L), 0)
+                        bnstat_done[pn] = (_vp(self.bn_part[L]), nrow, rbp(L))
                     else:
                         bwd.add(_lib.OP_CONV_DGRAD, n.name, p=(draw, wT, self._aptr(n.x, True)), flags=acc, conv=dbw,
                                 lane=L, reads=rdraw, writes=[rg(n.x)])
@@ -1523,7 +1451,7 @@ class Engine:
         argument of every bucket's op).  IFCBK_OPT_BUCKETS: target number of buckets (6), <= 1 = one launch at the end."""
         nb = int(os.environ.get('IFCBK_OPT_BUCKETS', '6'))
         whole = (bwd, opt, self._pack_multi(pack_ops))
-        if nb <= 1 or self.wgrad_side_lane:
+        if nb <= 1:
             return whole
         from .dp import segment_plan
         offs = [self._op_param_offsets(o) for o in bwd.ops]
@@ -1546,7 +1474,7 @@ class Engine:
         for o in pack_ops.ops:
             if o.p[2]:
                 owners.setdefault(skey((o.p[2] - sbase) // self.esize), []).append((o.p[0] - pbase) // 4)
-        dkinds = (_lib.OP_CONV_DGRAD, _lib.OP_CONV_DGRAD_BNSTAT, _lib.OP_CONV_DGRAD_BNSTAT_TAB)
+        dkinds = (_lib.OP_CONV_DGRAD, _lib.OP_CONV_DGRAD_BNSTAT)
         last_reader = {}                       # parameter offset -> index of the last backward op that reads its shadow
         shreads = {}                           # backward op index -> [('SH', off, off + size)]
         for k, o in enumerate(bwd.ops):

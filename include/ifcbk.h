@@ -312,21 +312,6 @@ IFCBK_API int ifcbk_bn_bwd_maxpool(ifcbk_ctx*, const ifcbk_pool_desc* d, const v
  * ifcbk_conv2d_dgrad + ifcbk_bn_bwd up to the summation order of the two per-channel sums.
  * Replaces autograd of [TV] BasicConv2d chains (inception.py), reference call site neuston_models.py:66-68,81-86.  */
 IFCBK_API int ifcbk_conv2d_dgrad_bnstat_mblocks(const ifcbk_conv_desc*);
-/* The same fusion when dx is the gradient of a CONCATENATION of several BatchNorm+ReLU outputs (an Inception block output whose only
- * consumer is the next block's sibling 1x1 GEMM): `table` (device memory) holds one entry per 8 channels of dx naming that chunk's
- * producer -- `raw`: the producing BatchNorm's input at this chunk's first channel, pixel 0 (pixel stride raw_ld elements); `stat`:
- * that channel's mean, with invstd / scale / shift at +stat_ld, +2 stat_ld, +3 stat_ld floats; raw == NULL: no BatchNorm producer
- * (a pooled slice), its sums are zero.  part [mblocks][2][C]: every producer reads its own column range with row stride C
- * (ifcbk_bn_bwd_partials_ld).  Replaces autograd through [TV] torch.cat(...) of InceptionA/B/C/D/E.forward (reference call site
- * neuston_models.py:66-68,81-86).                                                                                              */
-typedef struct {
-    const void*  raw;
-    const float* stat;
-    int32_t      raw_ld;
-    int32_t      stat_ld;
-} ifcbk_bs_chunk;
-IFCBK_API int ifcbk_conv2d_dgrad_bnstat_table(ifcbk_ctx*, const ifcbk_conv_desc*, const void* dy, const void* wT, void* dx,
-                                    const ifcbk_bs_chunk* table, float* part, void* stream);
 IFCBK_API int ifcbk_conv2d_dgrad_bnstat(ifcbk_ctx*, const ifcbk_conv_desc*, const void* dy, const void* wT, void* dx,
                               const void* prev_raw, int prev_ld, const float* prev_mean, const float* prev_invstd,
                               const float* prev_scale, const float* prev_shift, float* part, void* stream);
@@ -373,7 +358,7 @@ enum {
     IFCBK_OP_CONV_DGRAD_BNSTAT, IFCBK_OP_BN_BWD_PARTIALS, IFCBK_OP_BN_STATS, IFCBK_OP_AVGPOOL_AFFINE,
     IFCBK_OP_CONV_FWD_AFFINE_SEG,
     IFCBK_OP_SGD,            /* p: P, G, momentum buffer (nullable); i[0] = n; f: lr, momentum, weight decay, grad scale */
-    IFCBK_OP_CONV_DGRAD_BNSTAT_TAB,  /* p: dy, wT, dx, table, part (ifcbk_conv2d_dgrad_bnstat_table)                           */
+    IFCBK_OP_RETIRED_31,     /* retired (was the per-chunk-table dgrad + BatchNorm-backward sums); the slot keeps the numbering */
     IFCBK_OP_BIAS_RELU_BWD,  /* p: y, dy, dz, dbias; u.bn: M, C, ldx = ld(y), ldy = ld(dy), relu, dtype; i[0] = ld(dz)          */
     IFCBK_OP_DROPOUT,        /* p: x, mask (nullable), y; i[0] = n, i[1] = dtype; f[0] = scale; flags bit 0 accumulate           */
     IFCBK_OP_FLATTEN_CHW,    /* p: x, flat; i: N, HW, C, ldx | dtype << 32; flags bit 0 accumulate, bit 2 to_chw                 */

@@ -53,13 +53,13 @@ def match(o, cls):
     if cls == 'bnfin':
         return k == _lib.OP_BN_FINALIZE
     if cls == 'dgrad':
-        return k in (_lib.OP_CONV_DGRAD, _lib.OP_CONV_DGRAD_BNSTAT, _lib.OP_CONV_DGRAD_BNSTAT_TAB)
+        return k in (_lib.OP_CONV_DGRAD, _lib.OP_CONV_DGRAD_BNSTAT)
     if cls == 'bnbwd':
         return k in (_lib.OP_BN_BWD, _lib.OP_BN_BWD_PARTIALS, _lib.OP_BN_BWD_MAXPOOL)
     if cls == 'bnapply':
         return k in (_lib.OP_BN_APPLY, _lib.OP_BN_APPLY_MAXPOOL)
     if cls in ('dgrad35', 'dgrad17', 'dgrad8', 'dgradstem'):
-        if k not in (_lib.OP_CONV_DGRAD, _lib.OP_CONV_DGRAD_BNSTAT, _lib.OP_CONV_DGRAD_BNSTAT_TAB):
+        if k not in (_lib.OP_CONV_DGRAD, _lib.OP_CONV_DGRAD_BNSTAT):
             return False
         hw = d.H                        # the tensor the input gradient is written for
         return {'dgrad35': hw == 35, 'dgrad17': hw == 17, 'dgrad8': hw == 8, 'dgradstem': hw > 35}[cls]

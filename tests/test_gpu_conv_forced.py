@@ -4,7 +4,7 @@ kernel (conv_flat) -- FORCED onto shapes off inception's batch-256 set (``IFCBK_
 arithmetic: aten::conv2d under neuston_models.py:66-68 for every backbone, with --batch of neuston_net.py:324): M tails, K tails
 (K % (64*TN)), reduction tails (Kg % 64), 1x1 / 3x3 / 1x7 / 7x1 / stride-2 forward, padding, channel slices (ldx / ldy), every tile
 (MT 8 / 10, TN 2..4, KH 4..6) and every epilogue of conv_common.h: statistics (MODE 0), eval affine (+residual, +ReLU), accumulate,
-BN-backward sums of one producer (MODE 3), of a producer table (MODE 5), segmented destinations (MODE 4).  Each test asserts through
+BN-backward sums of one producer (MODE 3), segmented destinations (MODE 4).  Each test asserts through
 ``ifcbk_op_kernel`` that the forced kernel is what the dispatcher picked."""
 import ctypes as C
 import os
@@ -200,9 +200,9 @@ def _check_forward_and_input_gradient(ctx, case, lx, ly, prefix):
     assert _rel(part2[:, 1].sum(0).cpu(), (dz * xhat).sum((0, 1, 2))) < 1e-4
 
 
-def test_wide_tile_producer_table_and_segmented_epilogues(ctx, forced):
-    """MODE 5 (BN-backward sums of a CONCATENATION's producers through a per-chunk table) and MODE 4 (eval sibling GEMM: segments
-    with their own destination, stride and affine-or-raw switch) on the wide-tile kernel, shapes with M and K tails."""
+def test_wide_tile_segmented_epilogue(ctx, forced):
+    """MODE 4 (eval sibling GEMM: segments with their own destination, stride and affine-or-raw switch) on the wide-tile kernel,
+    shapes with M and K tails."""
     from ifcb_classifier_amd import _lib
     forced(IFCBK_CONV_BIG=2, IFCBK_CONV_BIG_MT=8, IFCBK_CONV_BIG_TN=3, IFCBK_CONV_FLAT=0, IFCBK_CONV_SLAB=0)
     case = (3, 168, 13, 11, 152, 1, 1, 1, 1, 0, 0)
@@ -211,39 +211,6 @@ def test_wide_tile_producer_table_and_segmented_epilogues(ctx, forced):
     d = _desc(case, P, Q, LDX, LDY)
     st = _lib.cur_stream()
     g = torch.Generator().manual_seed(9)
-    # ---- MODE 5: dx channels [0,64) come from producer A, [64,104) have no BatchNorm producer (a pooled slice), [104,168) from B
-    assert _kname(ctx, d, _lib.OP_CONV_DGRAD_BNSTAT_TAB).startswith('conv_pp2<') and _kname(ctx, d, _lib.OP_CONV_DGRAD_BNSTAT_TAB).endswith(', 5>')
-    rawA = _bf(torch.randn(N, H, W, 64, generator=g)).to(torch.bfloat16).cuda()
-    rawB = _bf(torch.randn(N, H, W, 80, generator=g)).to(torch.bfloat16).cuda()        # B's tensor is wider: its slice [8, 72) is used
-    statA = torch.stack([torch.randn(64, generator=g) * 0.2, torch.rand(64, generator=g) + 0.5, torch.rand(64, generator=g) + 0.5,
-                         torch.randn(64, generator=g) * 0.3]).cuda()                 # rows: mean, invstd, scale, shift
-    statB = torch.stack([torch.randn(64, generator=g) * 0.2, torch.rand(64, generator=g) + 0.5, torch.rand(64, generator=g) + 0.5,
-                         torch.randn(64, generator=g) * 0.3]).cuda()
-    tab = (_lib.BsChunk * (Cc // 8))()
-    for c8 in range(Cc // 8):
-        c = c8 * 8
-        if c < 64:
-            tab[c8].raw, tab[c8].stat, tab[c8].raw_ld, tab[c8].stat_ld = rawA.data_ptr() + 2 * c, statA.data_ptr() + 4 * c, 64, 64
-        elif c < 104:
-            tab[c8].raw, tab[c8].stat, tab[c8].raw_ld, tab[c8].stat_ld = None, None, 0, 0
-        else:
-            cb = c - 104
-            tab[c8].raw, tab[c8].stat, tab[c8].raw_ld, tab[c8].stat_ld = rawB.data_ptr() + 2 * (8 + cb), statB.data_ptr() + 4 * cb, 80, 64
-    tabd = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).cuda()
-    nrow = ctx.lib.ifcbk_conv2d_dgrad_bnstat_mblocks(C.byref(d))
-    part = torch.full((nrow, 2, Cc), float('nan'), device='cuda')
-    dx = torch.full((N, H, W, Cc), float('nan'), dtype=torch.bfloat16, device='cuda')
-    ctx.call('ifcbk_conv2d_dgrad_bnstat_table', C.byref(d), _lib.ptr(dyb), _lib.ptr(wT), _lib.ptr(dx), _lib.ptr(tabd), _lib.ptr(part), st)
-    torch.cuda.synchronize()
-    rdx = torch.nn.grad.conv2d_input((N, Cc, H, W), w, dy, 1, 0).permute(0, 2, 3, 1)
-    dxs = dx.float().cpu()
-    assert _rel(dxs, rdx) < 3e-3
-    s1, s2 = part[:, 0].sum(0).cpu(), part[:, 1].sum(0).cpu()
-    for lo, hi, raw, stt in ((0, 64, rawA.float().cpu(), statA.cpu()), (104, 168, rawB.float().cpu()[..., 8:72], statB.cpu())):
-        dz = torch.where(raw * stt[2] + stt[3] > 0, dxs[..., lo:hi], torch.zeros(()))
-        assert _rel(s1[lo:hi], dz.sum((0, 1, 2))) < 1e-4
-        assert _rel(s2[lo:hi], (dz * ((raw - stt[0]) * stt[1])).sum((0, 1, 2))) < 1e-4
-    assert s1[64:104].abs().max().item() == 0 and s2[64:104].abs().max().item() == 0
     # ---- MODE 4: three segments (affine+ReLU into a slice, raw, affine+ReLU), their own tensors and strides
     assert _kname(ctx, d, _lib.OP_CONV_FWD_AFFINE_SEG).startswith('conv_pp2<') and _kname(ctx, d, _lib.OP_CONV_FWD_AFFINE_SEG).endswith(', 4>')
     ksegs = [64, 40, 48]
