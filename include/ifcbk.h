@@ -251,6 +251,12 @@ IFCBK_API int ifcbk_roi_preprocess(ifcbk_ctx*, const ifcbk_roi_desc*, const uint
                          const int32_t* hs, const int32_t* ws, const uint8_t* flips, int max_h, int max_w,
                          void* out, uint8_t* out_u8 /*nullable: resized u8 [n,S,S,in_channels]*/, void* stream);
 IFCBK_API size_t ifcbk_roi_preprocess_workspace(const ifcbk_roi_desc*, int max_h, int max_w);
+/* per-image, per-channel integer moments of a u8 plane [n_img][pixels_per_img][channels] (channels 1..4):
+   out[i][c][0] = sum of v, out[i][c][1] = sum of v*v, exact (uint64); n_img = 0 is a no-op.
+ * x is typically out_u8 of ifcbk_roi_preprocess; mean = sum v / (255 n), population std from the two sums.
+ * Replaces np.mean / np.std over the ToTensor output of neuston_util.py:31-38 (CALC_IMG_NORM).                        */
+IFCBK_API int ifcbk_u8_channel_moments(ifcbk_ctx*, const uint8_t* x, int n_img, int64_t pixels_per_img,
+                                        int channels, uint64_t* out, void* stream);
 /* The stem conv straight from the resized u8 plane (grey ROIs: in_channels = 1).  convert('RGB') + ToTensor + Normalize
  * (+ [TV] transform_input) make three copies of one plane g under per-channel affines x_c = ab[c] * g + ab[3 + c]; the
  * 3x3 / stride-2 / unpadded / 32-channel Conv2d_1a of those is a one-plane conv plus a constant, so the [N,S,S,8] input
