@@ -1,0 +1,248 @@
+"""Per-element error bounds for the convolution kernels, against a float64 reference of the same operation.
+
+A plain helper module imported by the tests (like local_parity.py).  Everything here runs on the CPU in float64.
+
+The reference is computed from the operands the kernel read (bf16- or fp32-representable values), so it carries no error of its own
+that matters: every product of two bf16 or fp32 values and every sum below is exact to about 2^-53.
+
+Bound of one output element y whose exact value is y64 = sum of n products p_i, with A64 = sum |p_i| (the same convolution of the
+absolute values) and u = 2^-24 (fp32 unit roundoff):
+
+    |y - y64| <= 1/2 ulp_out(|y64| + e) + e,        e = 2 * gamma_n * A64,        gamma_n = n u / (1 - n u)
+
+* gamma_n * A64 bounds a fp32 sum of n terms in ANY order, split-K partial sums and their combine included: a summation tree of n
+  leaves is at most n - 1 adds deep, and one more rounding covers the products of fp32 operands (bf16 x bf16 products are exact
+  in fp32).  The factor 2 is a margin: the guides of this project document the fp32 MFMA as an fma chain, but not how the bf16
+  MFMA orders its internal additions.
+* n is the reduction length of that element: R*S*Cw for the forward, the taps that actually hit times K for the input gradient,
+  N*P*Q for the weight gradient.
+* 1/2 ulp_out is the final rounding to the output type, taken at |y64| + e so that a result just across a binade edge is covered.
+* Accumulating forms (dx += ..., dw += ...): the reference is old + y64, the old value joins the sum as one more term.  The kernels'
+  shared epilogue (conv_common.h) rounds the fresh contribution to the storage type before it adds the old value (the C tile is
+  staged in LDS in that type): one rounding for each operation, so a bf16 accumulate also allows 1/2 ulp_bf16 of the contribution.
+* Eval affine epilogue act(scale * acc + shift [+ res]): the conv result is rounded to the storage type first (the same staging),
+  then the multiply-add and the residual add are one fp32 rounding each, the ReLU is 1-Lipschitz, the store rounds once more.
+
+Bf16 outputs also get a sensitivity check, which the worst-case bound is too loose to replace: the fraction of elements where
+y != rne_bf16(y64) must be at most 1 %.  One fp32 accumulation rounded once lands near 1e-3; a bf16-rounded partial sum pushes it to
+tens of percent.  Where the epilogue rounds an intermediate by design (accumulate, affine), either rounding model is accepted
+(the single rounding of the exact value, or the designed rounding of the rounded conv value).
+
+Detection limit: 2 * gamma_n * A64 grows like n^1.5 for unit-variance operands, one term like n^-0.5 (filters scaled by
+1/sqrt(fan-in)) or like 1 (weight gradients).  A single dropped term stays visible for forward / input-gradient reductions up to
+several thousand terms and for weight gradients up to N*P*Q of about 2000; test_conv_bounds_cpu.py shows where.
+"""
+import math
+
+import torch
+import torch.nn.functional as F
+
+U = 2.0 ** -24
+MISMATCH_MAX = 0.01
+
+
+def gamma(n):
+    nu = n * U
+    return nu / (1.0 - nu)
+
+
+def _ulp(a, mant_bits, min_exp):
+    e = torch.floor(torch.log2(a.double().abs().clamp_min(2.0 ** min_exp)))
+    return torch.exp2(e - mant_bits)
+
+
+def ulp_bf16(a):
+    return _ulp(a, 7, -126)
+
+
+def ulp_f32(a):
+    return _ulp(a, 23, -126)
+
+
+def ulp(a, out):
+    return ulp_bf16(a) if out == 'bf16' else ulp_f32(a)
+
+
+def rne(t, out):
+    """round a float64 tensor to the output type (round to nearest even), back to float64"""
+    return t.to(torch.bfloat16 if out == 'bf16' else torch.float32).double()
+
+
+# ------------------------------------------------------------------------------------------------------ float64 references
+# x NCHW, w KCRS, dy NKPQ (any float dtype holding the kernel's operand values).  Results are in the kernels' layouts:
+# forward [N][P][Q][K], input gradient [N][H][W][C], weight gradient [K][R][S][C].  Each returns (ref, A, n).
+
+def fwd(x, w, stride=1, pad=0):
+    x, w = x.double(), w.double()
+    y = F.conv2d(x, w, None, stride, pad).permute(0, 2, 3, 1)
+    a = F.conv2d(x.abs(), w.abs(), None, stride, pad).permute(0, 2, 3, 1)
+    K, Cw, R, S = w.shape
+    return y, a, R * S * Cw
+
+
+def dgrad(dy, w, xshape, stride=1, pad=0):
+    dy, w = dy.double(), w.double()
+    g = torch.nn.grad.conv2d_input(xshape, w, dy, stride, pad).permute(0, 2, 3, 1)
+    a = torch.nn.grad.conv2d_input(xshape, w.abs(), dy.abs(), stride, pad).permute(0, 2, 3, 1)
+    N, C, H, W = xshape
+    K, _, R, S = w.shape
+    taps = torch.nn.grad.conv2d_input((N, 1, H, W), torch.ones(1, 1, R, S, dtype=torch.float64),
+                                      torch.ones(N, 1, dy.shape[2], dy.shape[3], dtype=torch.float64), stride, pad)
+    return g, a, (taps.permute(0, 2, 3, 1) * K).round()
+
+
+def wgrad(x, dy, wshape, stride=1, pad=0):
+    x, dy = x.double(), dy.double()
+    g = torch.nn.grad.conv2d_weight(x, wshape, dy, stride, pad).permute(0, 2, 3, 1)
+    a = torch.nn.grad.conv2d_weight(x.abs(), wshape, dy.abs(), stride, pad).permute(0, 2, 3, 1)
+    return g, a, dy.shape[0] * dy.shape[2] * dy.shape[3]
+
+
+# ------------------------------------------------------------------------------------------------------ reporting
+_FAMILY = {}          # family -> [worst ratio, worst mismatch fraction, checks, index into conftest.MEASURED]
+
+
+def _record(family, ratio, frac):
+    try:
+        import conftest
+    except ImportError:         # (imported outside pytest)
+        return
+    row = _FAMILY.get(family)
+    if row is None:
+        row = _FAMILY[family] = [0.0, None, 0, len(conftest.MEASURED)]
+        conftest.MEASURED.append('')
+    row[0] = max(row[0], ratio)
+    if frac is not None:
+        row[1] = frac if row[1] is None else max(row[1], frac)
+    row[2] += 1
+    conftest.MEASURED[row[3]] = 'conv bound %-44s worst err/bound %.3f  bf16 mismatch %s  (%d checks)' % (
+        family, row[0], '-' if row[1] is None else '%.2e' % row[1], row[2])
+
+
+class Result:
+    def __init__(self, ratio, frac, nbad, msg):
+        self.ratio, self.frac, self.nbad, self.msg = ratio, frac, nbad, msg
+
+    def __repr__(self):
+        return self.msg
+
+
+def _finish(name, family, got, want, err, bound, frac, dims, raise_=True):
+    err = torch.where(torch.isnan(err), torch.full_like(err, math.inf), err)
+    r = err / bound
+    bad = ~(err <= bound)
+    nbad = int(bad.sum())
+    i = int(torch.argmax(r.flatten()))
+    idx = tuple(int(v) for v in torch.unravel_index(torch.tensor(i), got.shape))
+    ratio = float(r.flatten()[i])
+    msg = '%s: %d of %d elements over the bound; worst at %s = %s: got %.8g want %.8g bound %.3g (err/bound %.3g)' % (
+        name, nbad, got.numel(), '(%s)' % ', '.join(dims), idx, float(got[idx]), float(want[idx]), float(bound[idx]), ratio)
+    if frac is not None:
+        msg += '; bf16 mismatch fraction %.3e (limit %.0e)' % (frac, MISMATCH_MAX)
+    res = Result(ratio, frac, nbad, msg)
+    if family is not None:
+        _record(family, ratio, frac)
+    if raise_:
+        assert nbad == 0 and (frac is None or frac <= MISMATCH_MAX), msg
+    return res
+
+
+def check(name, got, ref, A, n, out='bf16', old=None, dims=('n', 'p', 'q', 'k'), family=None, raise_=True):
+    """got: the kernel's output (any dtype, the reference's layout); ref, A, n: from fwd / dgrad / wgrad.  old: the destination's
+    value before an accumulating call (then the reference is old + ref)."""
+    got = got.detach().double().cpu()
+    ref, A = ref.double(), A.double()
+    n = torch.as_tensor(n, dtype=torch.float64)
+    e = 2.0 * gamma(n + 1) * A
+    if old is None:
+        want = ref
+        bound = 0.5 * ulp(want.abs() + e, out) + e
+        frac = float((got != rne(want, out)).double().mean()) if out == 'bf16' else None
+    else:
+        old = old.detach().double().cpu()
+        want = old + ref
+        e = 2.0 * gamma(n + 1) * (A + old.abs())
+        inter = 0.5 * ulp(ref.abs() + e, out) if out == 'bf16' else 0.0      # the contribution rounded before the add
+        bound = 0.5 * ulp(want.abs() + e + inter, out) + e + inter
+        frac = float(((got != rne(want, out)) & (got != rne(old + rne(ref, out), out))).double().mean()) if out == 'bf16' else None
+    return _finish(name, family, got, want, (got - want).abs(), bound, frac, dims, raise_)
+
+
+def check_affine(name, got, ref, A, n, scale, shift, res=None, relu=False, dims=('n', 'p', 'q', 'k'), family=None, raise_=True):
+    """bf16 y = act(scale[k] * conv + shift[k] (+ res)), scale / shift fp32 per output channel (last axis), res the bf16 residual"""
+    got = got.detach().double().cpu()
+    ref, A = ref.double(), A.double()
+    s, b = scale.detach().double().cpu(), shift.detach().double().cpu()
+    r = torch.zeros(()) if res is None else res.detach().double().cpu()
+    e = 2.0 * gamma(torch.as_tensor(n, dtype=torch.float64) + 1) * A
+    e_raw = e + 0.5 * ulp_bf16(ref.abs() + e)                      # the conv value as staged in bf16
+    lin = s * ref + b + r
+    mag = s.abs() * (ref.abs() + e_raw) + b.abs() + r.abs()
+    e_lin = s.abs() * e_raw + 2.0 * U * mag                           # multiply-add and residual add: one rounding each
+    act = (lambda t: t.clamp_min(0)) if relu else (lambda t: t)
+    want = act(lin)
+    bound = 0.5 * ulp_bf16(want.abs() + e_lin) + e_lin
+    alt = act(s * rne(ref, 'bf16') + b + r)
+    frac = float(((got != rne(want, 'bf16')) & (got != rne(alt, 'bf16'))).double().mean())
+    return _finish(name, family, got, want, (got - want).abs(), bound, frac, dims, raise_)
+
+
+def check_sums(name, got, terms, mags=None, ops=2, family=None, raise_=True):
+    """per-channel sums (the BatchNorm partial rows of an epilogue, summed over rows in float64) against float64 sums of the terms
+    [rows, channels] built from the kernel's own rounded outputs; bound gamma_(M + ops) * sum |term| (ops: roundings inside one term).
+    mags: magnitudes of the terms' operands when a term's own roundings act on larger values than the term (default |terms|)"""
+    got = got.detach().double().cpu()
+    terms = terms.double()
+    want = terms.sum(0)
+    M = terms.shape[0]
+    mags = terms.abs() if mags is None else mags.double()
+    bound = gamma(M + ops) * mags.sum(0) + 1e-30
+    return _finish(name, family, got, want, (got - want).abs(), bound, None, ('channel',), raise_)
+
+
+def check_bn_fwd_sums(name, part, yh, family=None):
+    """forward statistics: part [rows][2][K] fp32, yh [..., K] the kernel's rounded outputs"""
+    y = yh.detach().double().cpu().reshape(-1, yh.shape[-1])
+    p = part.detach().double().cpu().sum(0)
+    check_sums(name + ' sum', p[0], y, family=family)
+    check_sums(name + ' sumsq', p[1], y * y, family=family)
+
+
+def check_bn_bwd_sums(name, part, dx, raw, mean, invstd, bsc, bsh, family=None):
+    """MODE 3 sums of one producer: sum dz, sum dz * (raw - mean) * invstd with dz = dx where raw * bsc + bsh > 0.  dx: the kernel's
+    rounded input gradient; the activation test is evaluated in fp32 by the kernel: elements whose pre-activation is within a few
+    fp32 roundings of 0 may fall on either side, and their terms join the bound"""
+    C_ = dx.shape[-1]
+    d = dx.detach().double().cpu().reshape(-1, C_)
+    rw = raw.detach().double().cpu().reshape(-1, C_)
+    mu, ist, sc, sh = (t.detach().double().cpu() for t in (mean, invstd, bsc, bsh))
+    pre = rw * sc + sh
+    amb = pre.abs() <= 4 * U * ((rw * sc).abs() + sh.abs())
+    dz = torch.where(pre > 0, d, torch.zeros(()))
+    xh = (rw - mu) * ist
+    p = part.detach().double().cpu().sum(0)
+    m1 = dz.abs() + amb * d.abs() / (gamma(dz.shape[0] + 3))
+    m2 = dz.abs() * (rw.abs() + mu.abs()) * ist + amb * (d * xh).abs() / (gamma(dz.shape[0] + 3))
+    check_sums(name + ' sum dz', p[0], dz, m1, ops=3, family=family)
+    check_sums(name + ' sum dz*xhat', p[1], dz * xh, m2, ops=3, family=family)
+
+
+def family_of(kname, role):
+    """'conv_pp2<3, 10, 4, 0>' -> 'conv_pp2 fwd' (mode suffix kept where the template's last argument is the epilogue mode)"""
+    base = kname.split('<')[0]
+    return '%s %s' % (base, role)
+
+
+def kname(ctx, d, kind, flags=0, residual=False):
+    """the kernel ifcbk_op_kernel names for one conv op of descriptor d"""
+    import ctypes as C
+    from ifcb_classifier_amd import _lib
+    op = _lib.Op()
+    op.kind = kind
+    op.flags = flags
+    op.u.conv = d
+    if residual:
+        op.p[5] = 1
+    buf = C.create_string_buffer(128)
+    ctx.lib.ifcbk_op_kernel(C.byref(op), buf, 128)
+    return buf.value.decode()

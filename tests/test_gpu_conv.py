@@ -6,6 +6,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import conv_bounds as cb
+
 pytestmark = pytest.mark.gpu
 
 
@@ -105,6 +107,9 @@ def test_conv_fwd_dgrad_wgrad(ctx, case):
     s2 = part[:, 1].sum(0).cpu()
     assert torch.allclose(s1, yh.sum((0, 2, 3)), rtol=1e-4, atol=1e-3)
     assert torch.allclose(s2, (yh * yh).sum((0, 2, 3)), rtol=1e-4, atol=1e-3)
+    fam = lambda kind, role: cb.family_of(cb.kname(ctx, d, kind), role)
+    cb.check('fwd %s' % (case,), y, *cb.fwd(x, w, (sh, sw), (ph, pw)), family=fam(_lib.OP_CONV_FWD, 'fwd'))
+    cb.check_bn_fwd_sums('fwd stats %s' % (case,), part, y, family='conv fwd statistics')
     # ---- dgrad
     dyd = nhwc(dy)
     dx = torch.full((N, H, W, Cc), float('nan'), dtype=torch.bfloat16, device='cuda')
@@ -113,10 +118,14 @@ def test_conv_fwd_dgrad_wgrad(ctx, case):
     dxh = from_nhwc(dx)
     rdx = xr.grad
     assert (dxh - _bf(rdx)).abs().max().item() <= 0.5e-2 * rdx.abs().max().item() + 1e-6
+    dref = cb.dgrad(dy, w, x.shape, (sh, sw), (ph, pw))
+    cb.check('dgrad %s' % (case,), dx, *dref, dims=('n', 'h', 'w', 'c'), family=fam(_lib.OP_CONV_DGRAD, 'dgrad'))
+    first = dx.clone()
     # accumulate: second call doubles it
     ctx.call('ifcbk_conv2d_dgrad', C.byref(d), _lib.ptr(dyd), _lib.ptr(wT), _lib.ptr(dx), 1, st)
     torch.cuda.synchronize()
     assert (from_nhwc(dx) - 2 * _bf(rdx)).abs().max().item() <= 2e-2 * rdx.abs().max().item() + 1e-6
+    cb.check('dgrad += %s' % (case,), dx, *dref, old=first, dims=('n', 'h', 'w', 'c'), family=fam(_lib.OP_CONV_DGRAD, 'dgrad +='))
     # ---- wgrad (fp32 KRSC)
     dw = torch.full((K, R, S, Cc), float('nan'), dtype=torch.float32, device='cuda')
     ctx.reserve(ctx.lib.ifcbk_conv2d_wgrad_workspace(C.byref(d)))
@@ -125,6 +134,8 @@ def test_conv_fwd_dgrad_wgrad(ctx, case):
     rdw = wr.grad.permute(0, 2, 3, 1)
     err = (dw.cpu() - rdw).abs().max().item()
     assert err <= 2e-5 * max(1.0, rdw.abs().max().item()) * (N * P * Q) ** 0.5, err
+    cb.check('wgrad %s' % (case,), dw, *cb.wgrad(x, dy, w.shape, (sh, sw), (ph, pw)), out='f32', dims=('k', 'r', 's', 'c'),
+             family=fam(_lib.OP_CONV_WGRAD, 'wgrad'))
 
 
 @pytest.mark.parametrize('case', [(2, 32, 20, 149, 32, 3, 3, 1, 1, 0, 0), (2, 32, 21, 19, 64, 3, 3, 1, 1, 1, 1),
@@ -154,6 +165,12 @@ def test_row_streaming_kernel_affine_epilogue(ctx, case, relu):
     if relu:
         want = want.clamp_min(0)
     assert torch.equal(got, want.to(torch.bfloat16))
+    xc, wc = x.cpu().float().permute(0, 3, 1, 2), wk.cpu().float().permute(0, 3, 1, 2)
+    ref = cb.fwd(xc, wc, (sh, sw), (ph, pw))
+    assert cb.kname(ctx, d, _lib.OP_CONV_FWD_AFFINE).startswith('conv_rows3x3<')
+    cb.check('rows raw %s' % (case,), raw, *ref, family='conv_rows3x3 fwd')
+    cb.check_bn_fwd_sums('rows stats %s' % (case,), part, raw, family='conv fwd statistics')
+    cb.check_affine('rows affine %s relu %d' % (case, relu), got, *ref, scale, shift, relu=bool(relu), family='conv_rows3x3 affine')
 
 
 def test_conv_channel_slices(ctx):
@@ -223,6 +240,13 @@ def test_conv_fp32_parity_mode(ctx, case):
     assert torch.allclose(part[:, 0].sum(0).cpu(), yh.sum((0, 2, 3)), rtol=1e-4, atol=1e-3)
     assert rel(dx.cpu().permute(0, 3, 1, 2), xr.grad) < 1e-5
     assert rel(dw.cpu(), wr.grad.permute(0, 2, 3, 1)) < 1e-5
+    cb.check('f32 fwd %s' % (case,), y, *cb.fwd(x, w, (sh, sw), (ph, pw)), out='f32', family='conv_igemm<float> fwd')
+    cb.check_bn_fwd_sums('f32 fwd stats %s' % (case,), part, y, family='conv fwd statistics')
+    cb.check('f32 dgrad %s' % (case,), dx, *cb.dgrad(dy, w, x.shape, (sh, sw), (ph, pw)), out='f32', dims=('n', 'h', 'w', 'c'),
+             family='conv_igemm<float> dgrad')
+    assert cb.kname(ctx, d, _lib.OP_CONV_WGRAD).startswith('conv_wgrad_f32<')
+    cb.check('f32 wgrad %s' % (case,), dw, *cb.wgrad(x, dy, w.shape, (sh, sw), (ph, pw)), out='f32', dims=('k', 'r', 's', 'c'),
+             family='conv_wgrad_f32 wgrad')
 
 
 @pytest.mark.parametrize('case', [(2, 64, 9, 9, 96, 3, 3, 1, 1, 1, 1), (3, 192, 7, 7, 192, 1, 7, 1, 1, 0, 3),
@@ -268,5 +292,10 @@ def test_dgrad_bnstat_equals_dgrad_then_bn_bwd(ctx, case):
              _lib.ptr(db2), 0, st)
     torch.cuda.synchronize()
     assert torch.equal(dx, dx2)
+    w = wT.cpu().float().flip(1, 2).permute(3, 0, 1, 2)          # the forward filter [K][C][R][S]
+    dyc = dy.cpu().float().permute(0, 3, 1, 2)
+    fam = cb.family_of(cb.kname(ctx, d, _lib.OP_CONV_DGRAD_BNSTAT), 'dgrad bnstat')
+    cb.check('dgrad bnstat %s' % (case,), dx2, *cb.dgrad(dyc, w, (N, Cc, H, W), (sh, sw), (ph, pw)), dims=('n', 'h', 'w', 'c'), family=fam)
+    cb.check_bn_bwd_sums('dgrad bnstat %s' % (case,), part, dx2, raw, mean, invstd, scale, shift, family='conv dgrad BN-backward sums')
     for a, b in ((dg, dg2), (db, db2), (draw.float(), draw2.float())):
         assert (a - b).abs().max().item() <= 2e-3 * a.abs().max().item() + 1e-6, (a - b).abs().max().item()

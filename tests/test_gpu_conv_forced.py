@@ -13,6 +13,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import conv_bounds as cb
+
 pytestmark = pytest.mark.gpu
 
 
@@ -153,6 +155,10 @@ def _check_forward_and_input_gradient(ctx, case, lx, ly, prefix):
     assert torch.allclose(part[:, 1].sum(0).cpu(), (yh * yh).sum((0, 1, 2)), rtol=1e-4, atol=1e-3)
     if ly:
         assert torch.isnan(yb[..., :ly // 2].float()).all() and torch.isnan(yb[..., ly // 2 + K:].float()).all()
+    fam = lambda kind, role, **kw: cb.family_of(_kname(ctx, d, kind, **kw), role)
+    fref = cb.fwd(x, w, (sh, sw), (ph, pw))
+    cb.check('fwd %s' % (case,), yv, *fref, family=fam(_lib.OP_CONV_FWD, 'fwd'))
+    cb.check_bn_fwd_sums('fwd stats %s' % (case,), part, yv, family='conv fwd statistics')
     # ---- eval epilogue: affine + residual + ReLU
     g = torch.Generator().manual_seed(3)
     scale, shift = torch.rand(K, generator=g) + 0.5, torch.randn(K, generator=g) * 0.3
@@ -164,6 +170,8 @@ def _check_forward_and_input_gradient(ctx, case, lx, ly, prefix):
     torch.cuda.synchronize()
     want = torch.relu(_bf(yref) * scale + shift + res)          # the affine acts on the conv output as stored (rounded)
     assert _rel(y2v.float().cpu(), want) < 4e-3
+    cb.check_affine('affine+res %s' % (case,), y2v, *fref, scale, shift, res, relu=True,
+                    family=fam(_lib.OP_CONV_FWD_AFFINE, 'affine+res', residual=True))
     if sh != 1:
         return
     # ---- input gradient: first writer, accumulating, with the BN-backward sums of one producer (MODE 3)
@@ -175,10 +183,14 @@ def _check_forward_and_input_gradient(ctx, case, lx, ly, prefix):
     torch.cuda.synchronize()
     rdx = xr.grad.permute(0, 2, 3, 1)
     assert _rel(dxv.float().cpu(), rdx) < 3e-3
+    dref = cb.dgrad(dy, w, x.shape, (sh, sw), (ph, pw))
+    cb.check('dgrad %s' % (case,), dxv, *dref, dims=('n', 'h', 'w', 'c'), family=fam(_lib.OP_CONV_DGRAD, 'dgrad'))
     first = dxv.float().cpu().clone()
     ctx.call('ifcbk_conv2d_dgrad', C.byref(d), dyp, _lib.ptr(wT), dxp, 1, st)
     torch.cuda.synchronize()
     assert _rel(dxv.float().cpu(), 2 * first) < 6e-3
+    cb.check('dgrad += %s' % (case,), dxv, *dref, old=first, dims=('n', 'h', 'w', 'c'),
+             family=fam(_lib.OP_CONV_DGRAD, 'dgrad +=', flags=1))
     assert _kname(ctx, d, _lib.OP_CONV_DGRAD_BNSTAT).startswith(prefix) and _kname(ctx, d, _lib.OP_CONV_DGRAD_BNSTAT).endswith(', 3>')
     raw = _bf(torch.randn(N, H, W, Cc, generator=g) * 1.5)
     mean, invstd = torch.randn(Cc, generator=g) * 0.2, torch.rand(Cc, generator=g) + 0.5
@@ -198,6 +210,7 @@ def _check_forward_and_input_gradient(ctx, case, lx, ly, prefix):
     xhat = (raw - mean) * invstd
     assert _rel(part2[:, 0].sum(0).cpu(), dz.sum((0, 1, 2))) < 1e-4
     assert _rel(part2[:, 1].sum(0).cpu(), (dz * xhat).sum((0, 1, 2))) < 1e-4
+    cb.check_bn_bwd_sums('dgrad bnstat %s' % (case,), part2, dxs, raw, mean, invstd, bsc, bsh, family='conv dgrad BN-backward sums')
 
 
 def test_wide_tile_segmented_epilogue(ctx, forced):
@@ -231,6 +244,11 @@ def test_wide_tile_segmented_epilogue(ctx, forced):
     assert torch.isnan(ys[0][..., :16].float()).all() and torch.isnan(ys[0][..., 80:].float()).all()
     assert _rel(ys[1].float().cpu(), yref[..., 64:104]) < 3e-3
     assert _rel(ys[2].float().cpu(), act[..., 104:152]) < 4e-3
+    ref, A, n = cb.fwd(x, w)
+    fam = cb.family_of(_kname(ctx, d, _lib.OP_CONV_FWD_AFFINE_SEG), 'segments')
+    cb.check_affine('segment 0', ys[0][..., 16:80], ref[..., :64], A[..., :64], n, scale[:64], shift[:64], relu=True, family=fam)
+    cb.check('segment 1', ys[1], ref[..., 64:104], A[..., 64:104], n, family=fam)
+    cb.check_affine('segment 2', ys[2], ref[..., 104:], A[..., 104:], n, scale[104:], shift[104:], relu=True, family=fam)
 
 
 WGRAD = [
@@ -263,9 +281,13 @@ def test_wide_tile_weight_gradient_forced(ctx, forced, case, kh, lx, ly):
     assert _rel(dw.cpu(), rdw) < 1e-4
     err = (dw.cpu() - rdw).abs().max().item()
     assert err <= 2e-5 * max(1.0, rdw.abs().max().item()) * (N * P * Q) ** 0.5, err
+    wref = cb.wgrad(x, dy, w.shape, (sh, sw), (ph, pw))
+    cb.check('wgrad %s' % (case,), dw, *wref, out='f32', dims=('k', 'r', 's', 'c'), family='conv_wgrad_pp wgrad')
+    first = dw.clone()
     ctx.call('ifcbk_conv2d_wgrad', C.byref(d), xp, dyp, _lib.ptr(dw), 1, st)      # accumulate
     torch.cuda.synchronize()
     assert _rel(dw.cpu(), 2 * rdw) < 1e-4
+    cb.check('wgrad += %s' % (case,), dw, *wref, old=first, out='f32', dims=('k', 'r', 's', 'c'), family='conv_wgrad_pp wgrad +=')
 
 
 # the flat-slot weight gradient (conv_wgrad_flat.hip, round 5): one filter row per block, the x slab shared by the row's taps.  3x3
@@ -307,9 +329,12 @@ def test_flat_slot_weight_gradient_forced(ctx, forced, case, lx, ly):
     assert _rel(outs[0], rdw) < 1e-4
     err = (outs[0] - rdw).abs().max().item()
     assert err <= 2e-5 * max(1.0, rdw.abs().max().item()) * (N * P * Q) ** 0.5, err
+    wref = cb.wgrad(x, dy, w.shape, (sh, sw), (ph, pw))
+    cb.check('wgrad %s' % (case,), outs[0], *wref, out='f32', dims=('k', 'r', 's', 'c'), family='conv_wgrad_flat wgrad')
     ctx.call('ifcbk_conv2d_wgrad', C.byref(d), xp, dyp, _lib.ptr(dw), 1, st)      # accumulate
     torch.cuda.synchronize()
     assert _rel(dw.cpu(), 2 * rdw) < 1e-4
+    cb.check('wgrad += %s' % (case,), dw, *wref, old=outs[1], out='f32', dims=('k', 'r', 's', 'c'), family='conv_wgrad_flat wgrad +=')
 
 
 def test_flat_slot_weight_gradients_as_one_group(ctx, forced):
@@ -321,7 +346,7 @@ def test_flat_slot_weight_gradients_as_one_group(ctx, forced):
     n = len(cases)
     st = _lib.cur_stream()
     descs = (_lib.ConvDesc * n)()
-    xs, dys, dws, keep, single = (C.c_void_p * n)(), (C.c_void_p * n)(), (C.c_void_p * n)(), [], []
+    xs, dys, dws, keep, single, refs_g = (C.c_void_p * n)(), (C.c_void_p * n)(), (C.c_void_p * n)(), [], [], []
     for i, case in enumerate(cases):
         N, Cc, H, W, K, R, S, sh, sw, ph, pw = case
         x, w, dy, xb, dyb, wk, wT, P, Q, LDX, LDY = _tensors(case, 50 + i)
@@ -333,6 +358,7 @@ def test_flat_slot_weight_gradients_as_one_group(ctx, forced):
         ctx.call('ifcbk_conv2d_wgrad', C.byref(d), _lib.ptr(xb), _lib.ptr(dyb), _lib.ptr(dw1), 0, st)
         torch.cuda.synchronize()
         single.append(dw1.cpu())
+        refs_g.append(cb.wgrad(x, dy, w.shape, 1, case[9:]))
         dwg = torch.full((K, R, S, Cc), float('nan'), device='cuda')
         xs[i], dys[i], dws[i] = xb.data_ptr(), dyb.data_ptr(), dwg.data_ptr()
         keep.append((xb, dyb, dwg))
@@ -346,6 +372,7 @@ def test_flat_slot_weight_gradients_as_one_group(ctx, forced):
     for i in range(n):
         got = keep[i][2].cpu()
         assert _rel(got, single[i]) < 1e-6
+        cb.check('flat group member %d' % i, got, *refs_g[i], out='f32', dims=('k', 'r', 's', 'c'), family='conv_wgrad_flatg wgrad')
         # (the split counts of the group differ from the single launches': the same products summed in another split order)
 
 
@@ -397,6 +424,9 @@ def test_persistent_wide_tile_kernel_forced(ctx, forced, case, grid, lx, ly):
     assert torch.allclose(part[:, 1].sum(0).cpu(), (yh * yh).sum((0, 1, 2)), rtol=1e-4, atol=1e-3)
     if ly:
         assert torch.isnan(yb[..., :ly // 2].float()).all() and torch.isnan(yb[..., ly // 2 + K:].float()).all()
+    fref = cb.fwd(x, w, (sh, sw), (ph, pw))
+    cb.check('pp3 fwd %s grid %d' % (case, grid), yv, *fref, family='conv_pp3 fwd')
+    cb.check_bn_fwd_sums('pp3 fwd stats %s' % (case,), part, yv, family='conv fwd statistics')
     y1 = yb.clone()
     yb.fill_(float('nan'))
     part.fill_(float('nan'))
@@ -422,6 +452,7 @@ def test_persistent_wide_tile_kernel_forced(ctx, forced, case, grid, lx, ly):
         if relu:
             want = torch.relu(want)
         assert _rel(y2v.float().cpu(), want) < 4e-3
+        cb.check_affine('pp3 affine %s relu %d' % (case, relu), y2v, *fref, scale, shift, relu=bool(relu), family='conv_pp3 affine')
         # ... bit for bit what the LDS-staged epilogue of conv_pp2 / conv_igemm writes: a RUN batch gets the same scores whichever
         # kernel its size selects
         forced(IFCBK_CONV_PP3=0, IFCBK_CONV_FLAT=0, IFCBK_CONV_SLAB=0)
@@ -443,6 +474,7 @@ def test_persistent_wide_tile_kernel_forced(ctx, forced, case, grid, lx, ly):
     ctx.call('ifcbk_conv2d_dgrad', C.byref(d), dyp, _lib.ptr(wT), dxp, 0, st)
     torch.cuda.synchronize()
     assert _rel(dxv.float().cpu(), xr.grad.permute(0, 2, 3, 1)) < 3e-3
+    cb.check('pp3 dgrad %s' % (case,), dxv, *cb.dgrad(dy, w, x.shape, (sh, sw), (ph, pw)), dims=('n', 'h', 'w', 'c'), family='conv_pp3 dgrad')
     if lx:
         assert torch.isnan(dxb[..., :lx // 2].float()).all() and torch.isnan(dxb[..., lx // 2 + Cc:].float()).all()
 
@@ -466,7 +498,7 @@ def test_grouped_weight_gradient_forced(ctx, forced, kh, members):
     st = _lib.cur_stream()
     descs = (_lib.ConvDesc * n)()
     xs, dys, dws = (C.c_void_p * n)(), (C.c_void_p * n)(), (C.c_void_p * n)()
-    keep, refs, outs = [], [], []
+    keep, refs, outs, refs64 = [], [], [], []
     for i, (case, lx, ly) in enumerate(members):
         N, Cc, H, W, K, R, S, sh, sw, ph, pw = case
         x, w, dy, xb, dyb, wk, wT, P, Q, LDX, LDY = _tensors(case, 40 + i, lx, ly)
@@ -475,6 +507,7 @@ def test_grouped_weight_gradient_forced(ctx, forced, kh, members):
         xr, wr = x.clone().requires_grad_(True), w.clone().requires_grad_(True)
         F.conv2d(xr, wr, None, (sh, sw), (ph, pw)).backward(dy)
         refs.append((wr.grad.permute(0, 2, 3, 1), N * P * Q))
+        refs64.append(cb.wgrad(x, dy, w.shape, (sh, sw), (ph, pw)))
         xp, _ = _slice(xb, lx // 2, Cc)
         dyp, _ = _slice(dyb, ly // 2, K)
         dw = torch.full((K, R, S, Cc), float('nan'), device='cuda')
@@ -503,6 +536,8 @@ def test_grouped_weight_gradient_forced(ctx, forced, kh, members):
         assert _rel(o.cpu(), rdw) < 1e-4
         err = (o.cpu() - rdw).abs().max().item()
         assert err <= 2e-5 * max(1.0, rdw.abs().max().item()) * M ** 0.5, err
+    for i, o in enumerate(outs):
+        cb.check('ppg member %d' % i, o, *refs64[i], out='f32', dims=('k', 'r', 's', 'c'), family='conv_wgrad_ppg wgrad')
     for o in outs:
         o.fill_(float('nan'))
     ctx.run_program((_lib.Op * 1)(op), 1, st)                # the same launch through the program runner
@@ -513,6 +548,8 @@ def test_grouped_weight_gradient_forced(ctx, forced, kh, members):
     torch.cuda.synchronize()
     for o, (rdw, M) in zip(outs, refs):
         assert _rel(o.cpu(), 2 * rdw) < 1e-4
+    for i, o in enumerate(outs):
+        cb.check('ppg member %d +=' % i, o, *refs64[i], old=first[i], out='f32', dims=('k', 'r', 's', 'c'), family='conv_wgrad_ppg wgrad +=')
     # a member with another channel tile does not join
     bad = (_lib.ConvDesc * 2)(descs[0], _desc((2, 64, 9, 9, 64 if kh != 4 else 192, 3, 3, 1, 1, 1, 1), 9, 9, 64, 64 if kh != 4 else 192))
     if ctx.lib.ifcbk_conv2d_wgrad_group_member_kh(C.byref(bad[1])) != kh:
@@ -567,6 +604,9 @@ def test_flat_image_kernel_forced(ctx, forced, case, lx, ly):
         assert torch.allclose(part[:, 1].sum(0).cpu(), (yh * yh).sum((0, 1, 2)), rtol=1e-4, atol=1e-3)
         if ly:
             assert torch.isnan(yb[..., :ly // 2].float()).all() and torch.isnan(yb[..., ly // 2 + K:].float()).all()
+        fref = cb.fwd(x, w, 1, (ph, pw))
+        cb.check('flat fwd %s' % (case,), yv, *fref, family='conv_flat fwd')
+        cb.check_bn_fwd_sums('flat fwd stats %s' % (case,), part, yv, family='conv fwd statistics')
         scale, shift = torch.rand(K, generator=g) + 0.5, torch.randn(K, generator=g) * 0.3
         y2 = torch.full((N, P, Q, LDY), float('nan'), dtype=torch.bfloat16, device='cuda')
         y2p, y2v = _slice(y2, ly // 2, K)
@@ -574,6 +614,7 @@ def test_flat_image_kernel_forced(ctx, forced, case, lx, ly):
         ctx.call('ifcbk_conv2d_fwd_affine', C.byref(d), xp, _lib.ptr(wk), y2p, _lib.ptr(scd), _lib.ptr(shd), None, 0, 1, st)
         torch.cuda.synchronize()
         assert _rel(y2v.float().cpu(), torch.relu(_bf(yref) * scale + shift)) < 4e-3
+        cb.check_affine('flat affine %s' % (case,), y2v, *fref, scale, shift, relu=True, family='conv_flat affine')
     # ---- input gradient (the flat kernel in the swapped role: K -> C channels), plain and with the BN-backward sums (MODE 3)
     names = [_kname(ctx, d, _lib.OP_CONV_DGRAD), _kname(ctx, d, _lib.OP_CONV_DGRAD_BNSTAT)]
     assert (K, Cc, R) in ((64, 48, 5), (96, 64, 3), (96, 96, 3), (64, 96, 3))      # the input-gradient roles conv_flat.hip builds
@@ -584,6 +625,7 @@ def test_flat_image_kernel_forced(ctx, forced, case, lx, ly):
     torch.cuda.synchronize()
     first = dxv.float().cpu().clone()
     assert _rel(first, rdx) < 3e-3
+    cb.check('flat dgrad %s' % (case,), first, *cb.dgrad(dy, w, x.shape, 1, (ph, pw)), dims=('n', 'h', 'w', 'c'), family='conv_flat dgrad')
     if lx:
         assert torch.isnan(dxb[..., :lx // 2].float()).all() and torch.isnan(dxb[..., lx // 2 + Cc:].float()).all()
     raw = _bf(torch.randn(N, H, W, Cc, generator=g) * 1.5)
@@ -603,6 +645,7 @@ def test_flat_image_kernel_forced(ctx, forced, case, lx, ly):
     dz = torch.where(raw * bsc + bsh > 0, dxs, torch.zeros(()))
     assert _rel(part2[:, 0].sum(0).cpu(), dz.sum((0, 1, 2))) < 1e-4
     assert _rel(part2[:, 1].sum(0).cpu(), (dz * ((raw - mean) * invstd)).sum((0, 1, 2))) < 1e-4
+    cb.check_bn_bwd_sums('flat dgrad bnstat %s' % (case,), part2, dxs, raw, mean, invstd, bsc, bsh, family='conv dgrad BN-backward sums')
     # results do not depend on the launch: twice the same bits (deferred stores, per-block statistics in a fixed order)
     part3 = torch.full((nrow, 2, Cc), float('nan'), device='cuda')
     dx4 = torch.full((N, H, W, LDX), float('nan'), dtype=torch.bfloat16, device='cuda')
