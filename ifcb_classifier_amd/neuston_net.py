@@ -339,7 +339,14 @@ def do_training(args):
             yaml.safe_dump({k: (v if isinstance(v, (int, float, str, bool, list, type(None))) else str(v))
                             for k, v in vars(args).items()}, f)
     if args.onnx:
-        raise NotImplementedError('--onnx export is outside the MI355X hot path (SURVEY.md §2 row 8)')
+        # upstream exports its in-memory classifier as fit left it (not the best checkpoint); at the 224 pixels these backbones
+        # train at, where upstream's dummy input says 244
+        from . import onnx_export
+        output_path_onnx = os.path.join(args.outdir, args.model_id + '.onnx')
+        onnx_export.export(classifier.model.state_dict(), args.MODEL, args.classes, args.pretrained, output_path_onnx)
+        print('EXPORTED:', output_path_onnx)
+        onnx_export.write_classes(output_path_onnx + '.classes', args.classes)
+        print('EXPORTED:', output_path_onnx + '.classes')
 
 
 class _ImgSource:
