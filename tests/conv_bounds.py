@@ -102,21 +102,22 @@ def wgrad(x, dy, wshape, stride=1, pad=0):
 _FAMILY = {}          # family -> [worst ratio, worst mismatch fraction, checks, index into conftest.MEASURED]
 
 
-def _record(family, ratio, frac):
+def _record(family, ratio, frac, prefix='conv bound'):
+    """prefix: how the family's line in the measured section starts (tests/op_bounds.py records under 'op bound')"""
     try:
         import conftest
     except ImportError:         # (imported outside pytest)
         return
-    row = _FAMILY.get(family)
+    row = _FAMILY.get((prefix, family))
     if row is None:
-        row = _FAMILY[family] = [0.0, None, 0, len(conftest.MEASURED)]
+        row = _FAMILY[(prefix, family)] = [0.0, None, 0, len(conftest.MEASURED)]
         conftest.MEASURED.append('')
     row[0] = max(row[0], ratio)
     if frac is not None:
         row[1] = frac if row[1] is None else max(row[1], frac)
     row[2] += 1
-    conftest.MEASURED[row[3]] = 'conv bound %-44s worst err/bound %.3f  bf16 mismatch %s  (%d checks)' % (
-        family, row[0], '-' if row[1] is None else '%.2e' % row[1], row[2])
+    conftest.MEASURED[row[3]] = '%s %-44s worst err/bound %.3f  bf16 mismatch %s  (%d checks)' % (
+        prefix, family, row[0], '-' if row[1] is None else '%.2e' % row[1], row[2])
 
 
 class Result:
@@ -127,7 +128,7 @@ class Result:
         return self.msg
 
 
-def _finish(name, family, got, want, err, bound, frac, dims, raise_=True):
+def _finish(name, family, got, want, err, bound, frac, dims, raise_=True, prefix='conv bound'):
     err = torch.where(torch.isnan(err), torch.full_like(err, math.inf), err)
     r = err / bound
     bad = ~(err <= bound)
@@ -141,7 +142,7 @@ def _finish(name, family, got, want, err, bound, frac, dims, raise_=True):
         msg += '; bf16 mismatch fraction %.3e (limit %.0e)' % (frac, MISMATCH_MAX)
     res = Result(ratio, frac, nbad, msg)
     if family is not None:
-        _record(family, ratio, frac)
+        _record(family, ratio, frac, prefix)
     if raise_:
         assert nbad == 0 and (frac is None or frac <= MISMATCH_MAX), msg
     return res
@@ -187,17 +188,18 @@ def check_affine(name, got, ref, A, n, scale, shift, res=None, relu=False, dims=
     return _finish(name, family, got, want, (got - want).abs(), bound, frac, dims, raise_)
 
 
-def check_sums(name, got, terms, mags=None, ops=2, family=None, raise_=True):
+def check_sums(name, got, terms, mags=None, ops=2, family=None, raise_=True, n=None, prefix='conv bound'):
     """per-channel sums (the BatchNorm partial rows of an epilogue, summed over rows in float64) against float64 sums of the terms
     [rows, channels] built from the kernel's own rounded outputs; bound gamma_(M + ops) * sum |term| (ops: roundings inside one term).
-    mags: magnitudes of the terms' operands when a term's own roundings act on larger values than the term (default |terms|)"""
+    mags: magnitudes of the terms' operands when a term's own roundings act on larger values than the term (default |terms|).
+    n: the longest fp32 summation chain when it is shorter than the number of rows (fp32 row tiles combined in double)"""
     got = got.detach().double().cpu()
     terms = terms.double()
     want = terms.sum(0)
-    M = terms.shape[0]
+    M = terms.shape[0] if n is None else n
     mags = terms.abs() if mags is None else mags.double()
     bound = gamma(M + ops) * mags.sum(0) + 1e-30
-    return _finish(name, family, got, want, (got - want).abs(), bound, None, ('channel',), raise_)
+    return _finish(name, family, got, want, (got - want).abs(), bound, None, ('channel',), raise_, prefix)
 
 
 def check_bn_fwd_sums(name, part, yh, family=None):

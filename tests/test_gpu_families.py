@@ -246,12 +246,16 @@ def test_bias_relu_bwd_vs_torch(ctx, M, K, ld, relu, dtype):
     assert torch.equal(dz[:, :K].float(), want.to(td).float())
     assert (dz[:, K:] == 0).all()
     assert rel(db.cpu(), want.sum(0).cpu()) < 1e-5
+    import op_bounds as ob
+    ob.sums('bias_relu_bwd dbias', db, want.to(td).float().cpu(), ops=1, family='bias_relu_bwd')
+    db1 = db.clone()
     # accumulate into the parameter gradient, mask in place
     ctx.call('ifcbk_bias_relu_bwd', M, K, _lib.BF16 if dtype == 'bf16' else _lib.F32, _lib.ptr(y), ld, _lib.ptr(dy), ld,
              _lib.ptr(dy), ld, relu, _lib.ptr(db), 1, _lib.cur_stream())
     torch.cuda.synchronize()
     assert torch.equal(dy[:, :K], dz[:, :K])
     assert rel(db.cpu(), 2 * want.sum(0).cpu()) < 1e-5
+    ob.sums('bias_relu_bwd dbias accumulate', db, want.to(td).float().cpu(), ops=1, old=db1, family='bias_relu_bwd')
 
 
 def test_dropout_apply_and_flatten_chw_vs_torch(ctx):
@@ -267,6 +271,9 @@ def test_dropout_apply_and_flatten_chw_vs_torch(ctx):
     ctx.call('ifcbk_dropout_apply', n, _lib.BF16, _lib.ptr(x), None, 1.0, _lib.ptr(y), 1, _lib.cur_stream())       # eval copy, accumulating
     torch.cuda.synchronize()
     assert torch.equal(y, ((x.float() * mask.float() * 2).to(torch.bfloat16).float() + x.float()).to(torch.bfloat16))
+    import op_bounds as ob
+    y1 = (x.float() * mask.float() * 2).to(torch.bfloat16).double().cpu()
+    ob.elem('dropout_apply accumulate', y, y1 + x.double().cpu(), ob.U * (y1.abs() + x.double().cpu().abs()), 'bf16', 'dropout_apply')
     N, H, W, Cc, ld = 3, 6, 6, 16, 24
     t = torch.randn(N, H, W, ld, generator=g).to(torch.bfloat16).cuda()
     flat = torch.zeros(N, Cc * H * W, dtype=torch.bfloat16, device='cuda')
@@ -279,6 +286,8 @@ def test_dropout_apply_and_flatten_chw_vs_torch(ctx):
     torch.cuda.synchronize()
     assert torch.equal(back[..., :Cc], (t[..., :Cc].float() + 1).to(torch.bfloat16))
     assert (back[..., Cc:] == 1).all()
+    ob.elem('flatten_chw accumulate', back[..., :Cc], t[..., :Cc].double().cpu() + 1, ob.U * (t[..., :Cc].double().cpu().abs() + 1), 'bf16',
+            'flatten_chw', dims=('n', 'h', 'w', 'c'))
 
 
 def test_names_the_reference_rejects():

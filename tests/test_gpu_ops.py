@@ -10,6 +10,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import op_bounds as ob
+
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 
@@ -110,6 +112,8 @@ def test_nchw_to_nhwc_with_transform_input(ctx):
     assert (nchw(y)[:, :3] - _bf(ref)).abs().max().item() <= 2 ** -8 * ref.abs().max().item()
     assert ((nchw(y)[:, :3] != _bf(ref)).float().mean().item()) < 0.01
     assert nchw(y)[:, 3:].abs().max().item() == 0
+    want, e = ob.affine(x.permute(0, 2, 3, 1), torch.tensor(list(sc)), torch.tensor(list(sh)))
+    ob.elem('nchw_to_nhwc', y[..., :3], want, e, 'bf16', 'nchw_to_nhwc', dims=('n', 'h', 'w', 'c'))
 
 
 @pytest.mark.parametrize('N,Cc,H,W,ld,relu,res', [(4, 32, 9, 9, 32, 1, 0), (3, 96, 7, 5, 160, 1, 0), (2, 64, 6, 6, 64, 1, 1),
@@ -155,6 +159,11 @@ def test_bn_fwd_bwd_vs_oracle(ctx, N, Cc, H, W, ld, relu, res):
     yh = nchw(y)[:, :Cc]
     assert (yh - y_ref).abs().max().item() <= 2e-2 * y_ref.abs().max().item()
     assert ((yh - y_ref).abs() > 0).float().mean().item() < 0.02      # only rare 1-ulp bf16 flips
+    # per element, against float64 (tests/op_bounds.py)
+    ob.check_finalize('bn_finalize', dict(zip(('mean', 'invstd', 'scale', 'shift'), stats), running_mean=rm, running_var=rv),
+                      ob.finalize(part, M, eps, 0.1, gamma, beta, torch.zeros(Cc), torch.ones(Cc)), family='bn_finalize')
+    want, e = ob.affine(rows, stats[2], stats[3], None if resid is None else resid.permute(0, 2, 3, 1).reshape(M, Cc), bool(relu))
+    ob.elem('bn_apply', y[..., :Cc].reshape(M, Cc), want, e, 'bf16', 'bn_apply', dims=('m', 'c'))
     # backward (teacher-forced with the oracle's y so the ReLU mask is identical)
     yd = torch.zeros(N, H, W, ld, dtype=torch.bfloat16, device='cuda')
     yd[..., :Cc] = nhwc(y_ref)
@@ -172,6 +181,13 @@ def test_bn_fwd_bwd_vs_oracle(ctx, N, Cc, H, W, ld, relu, res):
     assert (nchw(dx) - d_raw).abs().max().item() <= 1e-2 * d_raw.abs().max().item()
     if res:
         assert (nchw(dresd) - _bf(dres)).abs().max().item() <= 1e-2 * dres.abs().max().item()
+    from test_gpu_op_bounds import bwd_rows
+    ref = ob.BnBwd(rows, gyd[..., :Cc].reshape(M, Cc), gamma, stats[0], stats[1], (1 if res else 2) if relu else 0, y=yd[..., :Cc].reshape(M, Cc),
+                   scale=stats[2], shift=stats[3], tile=bwd_rows(M, Cc, 0))
+    ref.check_params('bn_bwd', dgam, dbet, family='bn_bwd')
+    ref.check_dx('bn_bwd', dx.reshape(M, Cc), 'bf16', family='bn_bwd')
+    if res:
+        ref.check_dres('bn_bwd', dresd.reshape(M, Cc), 'bf16', family='bn_bwd')
 
 
 @pytest.mark.parametrize('N,Cc,H,W,pad,dtype', [(3, 64, 21, 21, 0, 0), (2, 192, 15, 13, 0, 0), (2, 64, 16, 16, 1, 0),
@@ -244,6 +260,7 @@ def test_bn_eval_scale_shift(ctx):
     torch.cuda.synchronize()
     s = gamma / torch.sqrt(rv + 1e-5)
     assert torch.allclose(sc.cpu(), s, rtol=1e-6) and torch.allclose(sh.cpu(), beta - rm * s, rtol=1e-5, atol=1e-6)
+    ob.check_finalize('bn_finalize eval', {'scale': sc, 'shift': sh}, ob.finalize_eval(1e-5, gamma, beta, rm, rv), family='bn_finalize (eval)')
 
 
 @pytest.mark.parametrize('kind,N,Cc,H,W,k,s,p', [('max', 2, 64, 15, 15, 3, 2, 0), ('max', 2, 64, 14, 14, 3, 2, 1),
@@ -278,6 +295,19 @@ def test_pool_fwd_bwd_vs_oracle(ctx, kind, N, Cc, H, W, k, s, p):
     else:
         assert (nchw(y) - y_ref).abs().max().item() <= 8e-3 * y_ref.abs().max().item()
     assert (nchw(dx) - _bf(dx_ref)).abs().max().item() <= 1e-2 * dx_ref.abs().max().item() + 1e-6
+    # per element, against float64 (tests/op_bounds.py)
+    geo = ob.Geo(H, W, k, k, s, s, p, p)
+    xl, gl = x.permute(0, 2, 3, 1), gy.permute(0, 2, 3, 1)
+    if kind == 'max':
+        yr, ar = ob.maxpool_fwd(xl, geo)
+        ob.exact('maxpool values', y, yr, 'maxpool')
+        ob.exact('maxpool arg-max', am, ar, 'maxpool')
+        bref = ob.maxpool_bwd(gl, am, geo, N, Cc)
+    else:
+        ob.check_sum('avgpool', y, *ob.avgpool_fwd(xl, geo), 'bf16', family='avgpool', dims=('n', 'p', 'q', 'c'))
+        bref = ob.avgpool_bwd(gl, geo, N, Cc)
+    ob.check_sum('pool bwd', dx, *bref, 'bf16', family=kind + 'pool')
+    dx1 = dx.clone()
     # accumulate
     if kind == 'max':
         ctx.call('ifcbk_maxpool_bwd', C.byref(d), _lib.ptr(gyd), _lib.ptr(am), _lib.ptr(dx), 1, st)
@@ -285,6 +315,7 @@ def test_pool_fwd_bwd_vs_oracle(ctx, kind, N, Cc, H, W, k, s, p):
         ctx.call('ifcbk_avgpool_bwd', C.byref(d), _lib.ptr(gyd), _lib.ptr(dx), 1, st)
     torch.cuda.synchronize()
     assert (nchw(dx) - 2 * dx_ref).abs().max().item() <= 3e-2 * dx_ref.abs().max().item() + 1e-6
+    ob.check_sum('pool bwd accumulate', dx, *bref, 'bf16', old=dx1, family=kind + 'pool')
 
 
 @pytest.mark.parametrize('N,HW,Cc,NC,drop', [(6, 64, 2048, 100, True), (5, 1, 768, 100, False), (3, 49, 512, 2, False)])
@@ -326,6 +357,18 @@ def test_head_loss_vs_oracle(ctx, N, HW, Cc, NC, drop):
     assert torch.allclose(dW.cpu(), dW_ref, rtol=1e-4, atol=1e-7)
     assert torch.allclose(dbb.cpu(), db_ref, rtol=1e-4, atol=1e-7)
     assert (nchw(dx) - dx_ref).abs().max().item() <= 1e-2 * dx_ref.abs().max().item()
+    # per element, against float64 and from the values each kernel read (tests/op_bounds.py)
+    xl = x.permute(0, 2, 3, 1).reshape(N, HW, Cc)
+    ob.check_sum('gap', featd, *ob.gap(xl, mask, 2.0), 'f32', family='head gap', dims=('n', 'c'))
+    ob.check_sum('fc', lg, *ob.fc_fwd(featd, W, b), 'f32', family='head fc', dims=('n', 'j'))
+    ob.check_dict('softmax_xent', {'loss': loss, 'dlogits': dl}, ob.xent(lg, tgt, 0.4, old_loss=5.0), family='softmax_xent')
+    pr, e = ob.softmax(lg)[:2]
+    ob.elem('softmax', probs, pr, e, 'f32', 'softmax', dims=('n', 'j'))
+    ob.check_sum('fc_wgrad', dW, *ob.fc_wgrad(dl, featd), 'f32', family='head fc_wgrad', dims=('j', 'c'))
+    ob.check_sum('fc_bgrad', dbb, *ob.fc_bgrad(dl), 'f32', family='head fc_bgrad', dims=('j',))
+    ref, A, n = ob.head_dx(dl, W, mask, 2.0, HW, Cc)
+    ex = lambda t: t[:, None, :].expand(N, HW, Cc)
+    ob.check_sum('head_dx', dx.reshape(N, HW, Cc), ex(ref), ex(A), n, 'bf16', family='head dx', dims=('n', 'hw', 'c'))
 
 
 def test_dropout_mask_rate_and_determinism(ctx):
@@ -353,9 +396,11 @@ def test_adam_matches_torch_adam_over_steps(ctx):
     for step in range(1, 4):
         gr = torch.randn(n, generator=g) * 10 ** (step - 2)
         gr_d = gr.cuda()
+        one = ob.adam(pd, gr, m, v, 1e-3, 0.9, 0.999, 1e-8, 0.0, step, 1.0)         # one step from the kernel's own state
         ctx.call('ifcbk_adam_flat', _lib.ptr(pd), _lib.ptr(gr_d), _lib.ptr(m), _lib.ptr(v), n, 1e-3, 0.9, 0.999, 1e-8,
                  0.0, step, 1.0, _lib.cur_stream())
         torch.cuda.synchronize()
+        ob.check_dict('adam step %d' % step, {'p': pd, 'm': m, 'v': v}, one, family='adam')
         pr, mr, vr = O.adam_step(pr, gr, mr, vr, step)
     torch.cuda.synchronize()
     assert (pd.cpu() - pr).abs().max().item() < 2e-6
@@ -387,6 +432,7 @@ def test_bn_stats_of_a_stored_tensor(ctx, N, Cc, H, W, ld, dtype):
     for r in range(rows):       # every partial row covers exactly its 1024 rows
         blk = xs[r * 1024:(r + 1) * 1024]
         assert torch.allclose(part[r, 0].double().cpu(), blk.sum(0), rtol=1e-5, atol=1e-3)
+    ob.check_stats('bn_stats', part, xs, family='bn_stats')
 
 
 def test_sgd_matches_torch_sgd_over_steps(ctx):
@@ -402,8 +448,11 @@ def test_sgd_matches_torch_sgd_over_steps(ctx):
         opt = torch.optim.SGD([pr], lr=0.05, momentum=mu)
         for step in range(4):
             gr = torch.randn(n, generator=g)
+            one = ob.sgd(pd, gr, mom if mu else None, 0.05, mu, 0.0, 1.0)           # one step from the kernel's own state
             ctx.call('ifcbk_sgd_flat', _lib.ptr(pd), _lib.ptr(gr.cuda()), _lib.ptr(mom) if mu else None, n, 0.05, mu, 0.0, 1.0,
                      _lib.cur_stream())
+            torch.cuda.synchronize()
+            ob.check_dict('sgd', dict({'p': pd}, **({'mom': mom} if mu else {})), one, family='sgd')
             pr.grad = gr.clone()
             opt.step()
         torch.cuda.synchronize()
