@@ -1,5 +1,8 @@
 // On-GPU ROI preprocessing: ragged u8 ROIs -> PIL-exact bilinear resize (antialiased, 8-bit fixed point,
-// horizontal pass then vertical pass with a u8 intermediate) -> /255 -> Normalize -> NHWC bf16.
+// two passes with a u8 intermediate) -> /255 -> Normalize -> NHWC bf16.
+// Pass order as Pillow's Image.resize picks it per image: horizontal then vertical, except vertical first for a ROI more
+// than 100 times as tall as wide that shrinks in height (`vfirst` below; the 8-bit intermediate makes the order visible by
+// one level).  Such a ROI is taller than S, so a kmax == 3 batch (fast3, roi_resize3_kernel) holds none.
 //
 // Restates Pillow's ImagingResample (libImaging/Resample.c: precompute_coeffs, normalize_coeffs_8bpc,
 // ImagingResampleHorizontal_8bpc / Vertical_8bpc) -- the arithmetic behind transforms.Resize([S,S]) at
@@ -105,6 +108,7 @@ __global__ __launch_bounds__(320) void roi_resize_kernel(RoiArgs a) {
     __shared__ uint8_t srow[LR][LW];
     const bool fast3 = a.cin == 1 && a.kmax == 3 && w <= (int)blockDim.x;          // block-uniform
     const bool lds_ok = !fast3 && a.cin == 1 && a.kmax <= LR && w <= LW;
+    const bool vfirst = h > 100 * w && h > a.S;                                    // block-uniform (per image)
     if (fast3) {
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
@@ -130,19 +134,47 @@ __global__ __launch_bounds__(320) void roi_resize_kernel(RoiArgs a) {
             for (int c = threadIdx.x; c < w; c += blockDim.x) srow[j][c] = src[(size_t)row * w + c];
         }
         __syncthreads();
-        int accv = 1 << (PRECISION_BITS - 1);
-        for (int j = 0; j < yn; ++j) {
+        if (vfirst) {
             int acch = 1 << (PRECISION_BITS - 1);
             for (int k = 0; k < xn; ++k) {
                 int col = xmin + k;
                 if (hflip) col = w - 1 - col;
-                acch += (int)srow[j][col] * th[(size_t)(2 + k) * TS];
+                int accv = 1 << (PRECISION_BITS - 1);
+                for (int j = 0; j < yn; ++j) accv += (int)srow[j][col] * tv[(size_t)(2 + j) * TS];
+                acch += clip8(accv) * th[(size_t)(2 + k) * TS];
             }
-            accv += clip8(acch) * tv[(size_t)(2 + j) * TS];
+            res[0] = clip8(acch);
+        } else {
+            int accv = 1 << (PRECISION_BITS - 1);
+            for (int j = 0; j < yn; ++j) {
+                int acch = 1 << (PRECISION_BITS - 1);
+                for (int k = 0; k < xn; ++k) {
+                    int col = xmin + k;
+                    if (hflip) col = w - 1 - col;
+                    acch += (int)srow[j][col] * th[(size_t)(2 + k) * TS];
+                }
+                accv += clip8(acch) * tv[(size_t)(2 + j) * TS];
+            }
+            res[0] = clip8(accv);
         }
-        res[0] = clip8(accv);
     } else
     for (int c = 0; c < a.cin; ++c) {
+        if (vfirst) {
+            int acch = 1 << (PRECISION_BITS - 1);
+            for (int k = 0; k < xn; ++k) {
+                int col = xmin + k;
+                if (hflip) col = w - 1 - col;
+                int accv = 1 << (PRECISION_BITS - 1);
+                for (int j = 0; j < yn; ++j) {
+                    int row = ymin + j;
+                    if (vflip) row = h - 1 - row;
+                    accv += (int)src[((size_t)row * w + col) * a.cin + c] * tv[(size_t)(2 + j) * TS];
+                }
+                acch += clip8(accv) * th[(size_t)(2 + k) * TS];
+            }
+            res[c] = clip8(acch);
+            continue;
+        }
         int accv = 1 << (PRECISION_BITS - 1);
         for (int j = 0; j < yn; ++j) {
             int row = ymin + j;

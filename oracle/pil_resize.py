@@ -6,11 +6,15 @@ dependency of the reference, pinned ``pillow==8.4.0`` in ``requirements/pkgs.hpc
   precompute_coeffs : per output index, support = max(scale,1), window [center-support, center+support],
                       triangle weights evaluated in double, normalised by their sum
   normalize_coeffs_8bpc : weights -> int, round half away from zero, PRECISION_BITS = 32-8-2 = 22
-  horizontal pass then vertical pass, each: acc = 1<<21 + sum(pixel*k); out = clip8(acc >> 22), with an
-  8-bit intermediate image between the passes.
+  two passes, each: acc = 1<<21 + sum(pixel*k); out = clip8(acc >> 22), with an 8-bit intermediate image
+  between the passes, which makes their order visible (differences of one level).
+  pass order : horizontal then vertical, except that ``Image.resize`` of the installed Pillow runs the vertical
+               pass first for an image that is more than 100 times as tall as wide and is reduced in height
+               (``vertical_first``; tests/golden/sweep_pass_order.py measured it on 14,455 grid points).
 
-Pinned against Pillow itself (installed, 12.2.0; bit-identical to 8.4.0 on this chain, SURVEY.md Appendix B
-probe 6) by ``tests/test_oracle_cpu.py`` and the committed ``tests/golden/pil_resize_*.npz`` vectors.
+Pinned against Pillow itself (installed, 12.2.0; SURVEY.md Appendix B probe 6 compared it with 8.4.0 on a few
+shapes, none of them in the vertical-first region: INTEGRATION.md) by ``tests/test_oracle_cpu.py``,
+``tests/test_roi_paths_cpu.py`` and the committed ``tests/golden/pil_resize_*`` vectors.
 TEST INFRASTRUCTURE ONLY.
 """
 import math
@@ -59,8 +63,24 @@ def _clip8(a):
     return np.clip(a >> PRECISION_BITS, 0, 255)
 
 
-def resize_bilinear_u8(img, out_h, out_w):
-    """img: uint8 [H,W] or [H,W,C] -> uint8 [out_h,out_w(,C)], bit-exact to PIL ``resize(..., BILINEAR)``."""
+def vertical_first(H, W, out_h):
+    """the pass order of ``Image.resize`` (installed Pillow): vertical pass first for very tall images that shrink in height"""
+    return H > W * 100 and out_h < H
+
+
+def resize_bilinear_u8(img, out_h, out_w, order=None):
+    """img: uint8 [H,W] or [H,W,C] -> uint8 [out_h,out_w(,C)], bit-exact to PIL ``resize(..., BILINEAR)``.
+    order: None = Pillow's own choice (``vertical_first``), 'hv' / 'vh' force one (for the tests that tell them apart)."""
+    if order is None:
+        a = np.asarray(img)
+        order = 'vh' if vertical_first(a.shape[0], a.shape[1], out_h) else 'hv'
+    if order == 'vh':
+        a = np.asarray(img, np.uint8)
+        return _resize_hv(_resize_hv(a, out_h, a.shape[1]), out_h, out_w)
+    return _resize_hv(img, out_h, out_w)
+
+
+def _resize_hv(img, out_h, out_w):
     img = np.asarray(img, np.uint8)
     squeeze = img.ndim == 2
     if squeeze:

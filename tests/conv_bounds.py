@@ -28,6 +28,8 @@ y != rne_bf16(y64) must be at most 1 %.  One fp32 accumulation rounded once land
 tens of percent.  Where the epilogue rounds an intermediate by design (accumulate, affine), either rounding model is accepted
 (the single rounding of the exact value, or the designed rounding of the rounded conv value).
 
+The u8 stem (conv_stem_u8.hip) has bounds of its own, counted from its source: see stem_u8_fwd / stem_u8_wgrad below.
+
 Detection limit: 2 * gamma_n * A64 grows like n^1.5 for unit-variance operands, one term like n^-0.5 (filters scaled by
 1/sqrt(fan-in)) or like 1 (weight gradients).  A single dropped term stays visible for forward / input-gradient reductions up to
 several thousand terms and for weight gradients up to N*P*Q of about 2000; test_conv_bounds_cpu.py shows where.
@@ -169,6 +171,21 @@ def check(name, got, ref, A, n, out='bf16', old=None, dims=('n', 'p', 'q', 'k'),
     return _finish(name, family, got, want, (got - want).abs(), bound, frac, dims, raise_)
 
 
+def check_e(name, got, want, e, out='bf16', alts=(), dims=('n', 'p', 'q', 'k'), family=None, raise_=True):
+    """|got - want| <= 1/2 ulp_out(|want| + e) + e per element, for an e counted elsewhere (the u8 stem); bf16: the fraction of
+    elements that differ from rne(want) (or from a designed rounding model in alts) is held to MISMATCH_MAX like check()"""
+    got, want = got.detach().double().cpu(), want.double()
+    e = torch.as_tensor(e, dtype=torch.float64).expand_as(want)
+    bound = 0.5 * ulp(want.abs() + e, out) + e + 1e-300
+    frac = None
+    if out == 'bf16':
+        match = got == rne(want, out)
+        for a in alts:
+            match = match | (got == rne(a.double(), out))
+        frac = float((~match).double().mean())
+    return _finish(name, family, got, want, (got - want).abs(), bound, frac, dims, raise_)
+
+
 def check_affine(name, got, ref, A, n, scale, shift, res=None, relu=False, dims=('n', 'p', 'q', 'k'), family=None, raise_=True):
     """bf16 y = act(scale[k] * conv + shift[k] (+ res)), scale / shift fp32 per output channel (last axis), res the bf16 residual"""
     got = got.detach().double().cpu()
@@ -227,6 +244,95 @@ def check_bn_bwd_sums(name, part, dx, raw, mean, invstd, bsc, bsh, family=None):
     m2 = dz.abs() * (rw.abs() + mu.abs()) * ist + amb * (d * xh).abs() / (gamma(dz.shape[0] + 3))
     check_sums(name + ' sum dz', p[0], dz, m1, ops=3, family=family)
     check_sums(name + ' sum dz*xhat', p[1], dz * xh, m2, ops=3, family=family)
+
+
+# ------------------------------------------------------------------------------------------------------ the u8 stem
+# conv_stem_u8.hip: y[k] = sum_t g_t We[k,t] + B[k],  We[k,t] = sum_c a_c w[k,t,c],  B[k] = sum_{t,c} b_c w[k,t,c]  (g: u8 pixels, exact;
+# w: the fp32 master filter [K][R][S][C]; a_c, b_c: the fp32 input affine).  Counted from the source, u = 2^-24:
+#   taps and bias in fp32 (both kernels):  We = w0 a0 + w1 a1 + w2 a2: at most 3 roundings on a term (3 fmas / 3 products and 2 adds);
+#       B: the same expression per tap, then 9 adds `b += ...`: at most 3 + 9 = 12.  Relative to the sums of MAGNITUDES, because both
+#       cancel in fp32:   e_w = gamma_3 T + gamma_12 Bb,   T = sum_t g_t sum_c |a_c w|,   Bb = sum_{t,c} |b_c w|.
+#   the accumulation acts on the computed taps and bias:  mag = G + |B| + e_w,   G = sum_t g_t |We|.
+#   stem_u8_fwd_kernel (fp32 storage, or Q < 32):  v = bias; 9 x v = fmaf(g_t, we_t, v): gamma_9 mag.
+#   stem_u8_fwd_mfma_kernel (bf16, Q >= 32):  split3 writes a tap as hi + mid + lo, three bf16 values rounded to nearest (unit roundoff
+#       2^-8), the two remainders exact in fp32: |w - hi| <= 2^-8 |w|, |r1 - mid| <= 2^-16 |w|, |r2 - lo| <= 2^-24 |w|: the pieces
+#       represent the tap to u |w| (two pieces: 2^-16 |w|, which this bound must reject -- test_conv_bounds_cpu.py).  Then 27 + 3 exact
+#       bf16 x bf16 products in two chained MFMAs of 16 slots: 32 terms in an order the guides do not document, so gamma_33 in any
+#       order with the factor 2 of check(); the pieces' magnitudes add up to at most (1 + 2^-7) |w|:
+#           e = e_w + u mag + 2 gamma_33 (1 + 2^-7) mag.
+#   eval epilogue (both): act(fmaf(v, scale, shift)) on the fp32 v: e_lin = |scale| e + u (|scale ref| + |scale| e + |shift|).
+#   weight gradient dw[k,t,c] = a_c A[k,t] + b_c S[k],  A = sum dy g_t,  S = sum dy  (products exact: dy bf16 / fp32 times an integer
+#       <= 255 inside an fma, or bf16 x bf16 in the MFMA).  fp32 chain of one block partial: stem_u8_wgrad_kernel 32 fmas per thread
+#       (PIXB / 64 trips) + 4 shuffle adds + 2 adds across the waves = 38; stem_u8_wgrad_mfma_kernel: a wave runs 2 gpr MFMAs of 32
+#       terms (RB gpr / 4 items, gpr = ceil(Q / 32)) + 2 adds: 64 gpr + 2 terms, any order, factor 2.  stem_u8_wgrad_reduce_kernel adds
+#       the block partials and forms a_c A + b_c S in double (d = 2^-53 per operation) and rounds once to fp32:
+#           e = c gamma_n mag + (blocks + 3) d mag,   mag = |a_c| sum |dy| g_t + |b_c| sum |dy|   (a_c g and b_c cancel inside x_c:
+#           relative to |a| g + |b|, not to |x_c|), then the store (1/2 ulp_fp32); accumulating: the rounded value joins old in one add.
+STEM_K, STEM_PIXB, STEM_RB = 32, 2048, 8
+
+
+def stem_mfma(dtype, Q):
+    """conv_stem_u8.hip: stem_mfma"""
+    return dtype == 'bf16' and Q >= 32
+
+
+def stem_rows(N, P, Q, dtype):
+    """ifcbk_stem_u8_rows: the grid of both passes"""
+    return (N * P + STEM_RB - 1) // STEM_RB if stem_mfma(dtype, Q) else (N * P * Q + STEM_PIXB - 1) // STEM_PIXB
+
+
+def stem_u8_fwd(g, w, ab, mfma, pieces=3):
+    """g [N][H][W] u8, w [K][3][3][3] fp32 master, ab the six fp32 affine values -> (ref, e), [N][P][Q][K] float64.
+    pieces: bf16 pieces per tap in the MFMA kernel (3 in the source)"""
+    g = g.detach().double().cpu()[:, None]
+    w = w.detach().double().cpu()
+    ab = ab.detach().double().cpu()
+    wa, wb = w * ab[:3], w * ab[3:]
+    we, B, Bb = wa.sum(-1), wb.sum((1, 2, 3)), wb.abs().sum((1, 2, 3))
+    conv = lambda k: F.conv2d(g, k[:, None], None, 2).permute(0, 2, 3, 1)
+    ref, G, T = conv(we) + B, conv(we.abs()), conv(wa.abs().sum(-1))
+    e_w = gamma(3) * T + gamma(12) * Bb
+    mag = G + B.abs() + e_w
+    if mfma:
+        e = e_w + 2.0 ** (-8 * pieces) * mag + 2.0 * gamma(33) * (1 + 2.0 ** -7) * mag
+    else:
+        e = e_w + gamma(9) * mag
+    return ref, e
+
+
+def stem_affine(ref, e, scale, shift, relu):
+    """(want, e_lin) of act(fmaf(v, scale, shift))"""
+    s, b = scale.detach().double().cpu(), shift.detach().double().cpu()
+    lin = s * ref + b
+    e_lin = s.abs() * e + U * ((s * ref).abs() + s.abs() * e + b.abs())
+    return (lin.clamp_min(0) if relu else lin), e_lin
+
+
+def stem_u8_wgrad(g, dy, ab, mfma):
+    """g [N][H][W] u8, dy [N][P][Q][K] (the values the kernel read) -> (ref, e), [K][3][3][3] float64"""
+    g = g.detach().double().cpu()[:, None]
+    d = dy.detach().double().cpu().permute(0, 3, 1, 2).contiguous()
+    ab = ab.detach().double().cpu()
+    N, K, P, Q = d.shape
+    A = torch.nn.grad.conv2d_weight(g, (K, 1, 3, 3), d, 2)[:, 0]                      # [K][3][3]
+    Aa = torch.nn.grad.conv2d_weight(g, (K, 1, 3, 3), d.abs(), 2)[:, 0]
+    S, Sa = d.sum((0, 2, 3)), d.abs().sum((0, 2, 3))
+    ref = A[..., None] * ab[:3] + S[:, None, None, None] * ab[3:]
+    mag = Aa[..., None] * ab[:3].abs() + Sa[:, None, None, None] * ab[3:].abs()
+    gpr = (Q + 31) // 32
+    c, n = (2.0, 64 * gpr + 2) if mfma else (1.0, STEM_PIXB // 64 + 6)
+    blocks = (N * P + STEM_RB - 1) // STEM_RB if mfma else (N * P * Q + STEM_PIXB - 1) // STEM_PIXB
+    e = c * gamma(n) * mag + (blocks + 3) * 2.0 ** -53 * mag
+    return ref, e
+
+
+def check_stem_wgrad(name, got, ref, e, old=None, family=None, raise_=True):
+    """dw fp32 [K][3][3][3]; old: the destination before an accumulating call (the fresh value is rounded to fp32, then added)"""
+    if old is None:
+        return check_e(name, got, ref, e, 'fp32', dims=('k', 'r', 's', 'c'), family=family, raise_=raise_)
+    old = old.detach().double().cpu()
+    e2 = e + 0.5 * ulp_f32(ref.abs() + e)
+    return check_e(name, got, old + ref, e2, 'fp32', dims=('k', 'r', 's', 'c'), family=family, raise_=raise_)
 
 
 def family_of(kname, role):

@@ -186,3 +186,151 @@ def test_statistics_sums():
     part[7, :, 3] = 0                                  # one partial row of one channel not written (a 128-pixel tile lost)
     with pytest.raises(AssertionError, match='sum: 1 of 24'):
         cb.check_bn_fwd_sums('bn', part, y)
+
+
+# ------------------------------------------------------------------------------------------------------ the u8 stem
+# conv_stem_u8.hip emulated step by step in torch on the CPU (fp32 operations as the kernels order them); the bounds of
+# conv_bounds.stem_u8_fwd / stem_u8_wgrad accept the emulation and reject its subtly wrong variants.
+AB = (0.458 / (255 * 0.229), 0.448 / (255 * 0.224), 0.45 / (255 * 0.225), -0.03 - 0.458 * 0.485 / 0.229, -0.088 - 0.448 * 0.456 / 0.224,
+      -0.188 - 0.45 * 0.406 / 0.225)
+
+
+def _fma(a, b, c):
+    """fp32 a * b + c rounded once (the product of a u8 or bf16 value and an fp32 value is exact in double)"""
+    return (a.double() * b.double() + c.double()).float()
+
+
+def _stem_case(N=3, H=41, W=75, seed=0):
+    gen = torch.Generator().manual_seed(seed)
+    g = torch.randint(0, 256, (N, H, W), generator=gen, dtype=torch.uint8)
+    w = torch.randn(32, 3, 3, 3, generator=gen) * 0.2
+    return g, w, torch.tensor(AB, dtype=torch.float32)
+
+
+def _stem_taps(w, ab):
+    """the kernels' fp32 effective taps [K][9] and bias [K]"""
+    wk = w.reshape(32, 9, 3)
+    we = _fma(wk[..., 2], ab[2], _fma(wk[..., 1], ab[1], wk[..., 0] * ab[0]))
+    b = torch.zeros(32)
+    for t in range(9):
+        b = b + _fma(wk[:, t, 2], ab[5], _fma(wk[:, t, 1], ab[4], wk[:, t, 0] * ab[3]))
+    return we, b
+
+
+def _stem_patches(g):
+    N, H, W = g.shape
+    cols = torch.nn.functional.unfold(g.float()[:, None], (3, 3), stride=2)        # [N, 9, P*Q]
+    P, Q = (H - 3) // 2 + 1, (W - 3) // 2 + 1
+    return cols.permute(0, 2, 1).reshape(N, P, Q, 9), P, Q
+
+
+def _split(x, pieces):
+    out, r = [], x.clone()
+    for _ in range(pieces):
+        p = _bf(r)
+        out.append(p)
+        r = r - p
+    return out
+
+
+def _stem_fwd_vector(g, w, ab):
+    we, b = _stem_taps(w, ab)
+    pt, P, Q = _stem_patches(g)
+    v = b.expand(*pt.shape[:3], 32).clone()
+    for t in range(9):
+        v = _fma(pt[..., t:t + 1], we[:, t], v)
+    return v
+
+
+def _stem_fwd_mfma(g, w, ab, pieces=3):
+    """27 + 3 exact products summed in fp32, slot by slot in the order of the two MFMA operands"""
+    we, b = _stem_taps(w, ab)
+    pt, P, Q = _stem_patches(g)
+    wp, bp = _split(we, pieces), _split(b, pieces)
+    acc = torch.zeros(*pt.shape[:3], 32)
+    for piece in wp[:1] + bp + wp[1:]:
+        if piece.dim() == 1:
+            acc = acc + piece
+        else:
+            for t in range(9):
+                acc = acc + pt[..., t:t + 1] * piece[:, t]
+    return acc
+
+
+@pytest.mark.parametrize('out', ['bf16', 'fp32'])
+def test_stem_forward_bound_accepts_the_vector_emulation_and_rejects_one_storage_ulp(out):
+    g, w, ab = _stem_case()
+    ref, e = cb.stem_u8_fwd(g, w, ab, mfma=False)
+    tdt = torch.bfloat16 if out == 'bf16' else torch.float32
+    y = _stem_fwd_vector(g, w, ab).to(tdt)
+    r = cb.check_e('vector', y, ref, e, out)
+    assert r.ratio < 1 and (r.frac is None or r.frac < cb.MISMATCH_MAX)
+    bad = y.clone().float()
+    x = bad[1, 7, 11, 5]
+    # one storage ulp in bf16; in fp32 storage the counted roundings are themselves ~200 u of the magnitudes: 2^-15 there
+    bad[1, 7, 11, 5] = x + (float(cb.ulp(x.double().abs(), out)) if out == 'bf16' else 2.0 ** -15)
+    assert cb.check_e('ulp', bad, ref, e, out, raise_=False).nbad == 1
+    # the eval epilogue: scale and shift of the wrong channel
+    sc, sh = torch.rand(32) + 0.5, torch.randn(32) * 0.3
+    want, e_lin = cb.stem_affine(ref, e, sc, sh, True)
+    ya = _fma(_stem_fwd_vector(g, w, ab), sc, sh).clamp_min(0).to(tdt)
+    assert cb.check_e('affine', ya, want, e_lin, out).ratio < 1
+    yb = _fma(_stem_fwd_vector(g, w, ab), sc.roll(1), sh).clamp_min(0).to(tdt)
+    assert cb.check_e('affine', yb, want, e_lin, out, raise_=False).nbad > 0
+    # a border: the last output column computed from the column before it
+    bad = y.clone()
+    bad[:, :, -1] = bad[:, :, -2]
+    assert cb.check_e('border', bad, ref, e, out, raise_=False).nbad > 0
+
+
+def test_stem_mfma_bound_accepts_three_bf16_pieces_and_rejects_two():
+    """the split of a tap into bf16 pieces: three represent it to 2^-24 (the bound's term u * mag), two only to 2^-16.  The pieces'
+    error is invisible in the bf16 OUTPUT of a single element's rounding, so the bound is held against the fp32 accumulator here
+    (out='fp32'), and on the GPU against the stored bf16 value, where it shows as the mismatch fraction and the bound together"""
+    g, w, ab = _stem_case(N=4, H=75, W=75, seed=1)
+    ref, e = cb.stem_u8_fwd(g, w, ab, mfma=True)
+    acc3, acc2 = _stem_fwd_mfma(g, w, ab, 3), _stem_fwd_mfma(g, w, ab, 2)
+    r3 = cb.check_e('three pieces', acc3, ref, e, 'fp32')
+    assert r3.ratio < 1
+    r2 = cb.check_e('two pieces', acc2, ref, e, 'fp32', raise_=False)
+    assert r2.nbad > 0 and r2.ratio > 1, r2
+    rb = cb.check_e('three pieces, bf16 store', acc3.to(torch.bfloat16), ref, e, 'bf16')
+    assert rb.frac < cb.MISMATCH_MAX
+
+
+def _stem_wgrad_emulated(g, dy, ab, drop=None):
+    """fp32 partial sums per 32 pixels (sequential), combined in double, a_c A + b_c S rounded once"""
+    pt, P, Q = _stem_patches(g)
+    d = dy.float()
+    if drop is not None:
+        n, p, q0 = drop
+        d = d.clone()
+        d[n, p, q0:] = 0
+    cols = torch.cat([pt, torch.ones(*pt.shape[:3], 1)], -1).reshape(-1, 10)                  # [M, 10]
+    dm = d.reshape(-1, 32)
+    tot = torch.zeros(32, 10, dtype=torch.float64)
+    for i in range(0, cols.shape[0], 32):
+        acc = torch.zeros(32, 10)
+        for j in range(i, min(i + 32, cols.shape[0])):
+            acc = acc + dm[j][:, None] * cols[j][None]
+        tot += acc.double()
+    a = ab.double()
+    return (tot[:, :9].reshape(32, 3, 3, 1) * a[:3] + tot[:, 9].reshape(32, 1, 1, 1) * a[3:]).float()
+
+
+@pytest.mark.parametrize('mfma', [False, True])
+def test_stem_wgrad_bound_rejects_a_missing_last_pixel_group_of_one_row(mfma):
+    g, w, ab = _stem_case(N=2, H=21, W=83, seed=2)                    # Q = 41: groups of 32 + 9
+    P, Q = 10, 41
+    dy = _bf(torch.randn(2, P, Q, 32, generator=torch.Generator().manual_seed(3)))
+    ref, e = cb.stem_u8_wgrad(g, dy, ab, mfma)
+    good = _stem_wgrad_emulated(g, dy, ab)
+    assert cb.check_stem_wgrad('good', good, ref, e).ratio < 1
+    bad = _stem_wgrad_emulated(g, dy, ab, drop=(1, 4, 32))
+    r = cb.check_stem_wgrad('dropped group', bad, ref, e, raise_=False)
+    assert r.nbad > 32 * 27 // 2, r
+    one = _stem_wgrad_emulated(g, dy, ab, drop=(1, 9, 40))           # the last pixel of the last row alone
+    assert cb.check_stem_wgrad('dropped pixel', one, ref, e, raise_=False).nbad > 0
+    base = torch.randn(32, 3, 3, 3)
+    assert cb.check_stem_wgrad('acc', base + good, ref, e, old=base).ratio < 1
+    assert cb.check_stem_wgrad('acc twice', base + good + good, ref, e, old=base, raise_=False).nbad > 0

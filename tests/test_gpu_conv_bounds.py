@@ -330,7 +330,9 @@ INVENTORY = {
     'conv_wgrad_rows<3>', 'conv_wgrad_rows<4>', 'conv_wgrad_ppg', 'conv_wgrad_flatg',
 }
 # compared against fp64 or bit for bit against bound-checked kernels by their own tests (not rewritten here)
-COUNTED = {'stem_u8_fwd_kernel': 'test_gpu_stem_u8.py (fp64 reference)', 'stem_u8_wgrad_kernel': 'test_gpu_stem_u8.py (fp64 reference)',
+_STEM = 'test_gpu_stem_u8.py::test_stem_u8_kernels_vs_fp64_conv_of_the_three_affine_planes (conv_bounds.stem_u8_%s, per element)'
+COUNTED = {'stem_u8_fwd_kernel': _STEM % 'fwd', 'stem_u8_fwd_mfma_kernel': _STEM % 'fwd', 'stem_u8_wgrad_kernel': _STEM % 'wgrad',
+           'stem_u8_wgrad_mfma_kernel': _STEM % 'wgrad', 'stem_u8_wgrad_reduce_kernel': _STEM % 'wgrad',
            'conv_rows3x3/pool': 'test_gpu_conv_pool.py (bit-equal to conv_rows3x3 affine + max pool)'}
 
 

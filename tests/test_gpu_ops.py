@@ -71,6 +71,12 @@ def test_roi_resize_bit_exact_vs_pil_golden(ctx, S):
     for ch in range(3):
         assert torch.equal(o[..., ch], ref)
     assert o[..., 3:].abs().max().item() == 0
+    # the batch above has maxima 1024 x 1000 (kmax 9): every ROI took roi_resize_kernel's generic loop.  Each ROI again in a batch
+    # of its own, down the path its own size selects (roi_resize3_kernel, lds_ok, generic; tests/test_gpu_roi_paths.py has the rest)
+    for i, c in enumerate(meta):
+        o1, u1 = _roi_batch([rois[i]], S, ctx)
+        assert hashlib.sha256(u1.cpu().numpy()[0, :, :, 0].tobytes()).hexdigest() == c['sha256'], c
+        assert torch.equal(o1[0], out[i]), c
 
 
 def test_roi_flips_normalize_and_rgb_vs_oracle(ctx):

@@ -7,7 +7,8 @@ import ctypes as C
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
+
+import conv_bounds as cb
 
 pytestmark = pytest.mark.gpu
 
@@ -20,30 +21,42 @@ def _ab(mean, std, tsc=(1, 1, 1), tsh=(0, 0, 0)):
     return [tsc[c] / (255.0 * std[c]) for c in range(3)] + [tsh[c] - tsc[c] * mean[c] / std[c] for c in range(3)]
 
 
-@pytest.mark.parametrize('N,H,W,dtype', [(3, 299, 299, 'bf16'), (2, 31, 37, 'bf16'), (5, 64, 64, 'fp32'), (1, 33, 9, 'fp32'),
-                                         (40, 75, 75, 'bf16'), (2, 69, 67, 'bf16'), (3, 90, 131, 'bf16')])
-def test_stem_u8_kernels_vs_fp64_conv_of_the_three_affine_planes(N, H, W, dtype):
+def _family(kernel, dtype, Q):
+    """the kernel conv_stem_u8.hip launches for this storage type and row width (stem_mfma)"""
+    return kernel.replace('_kernel', '_mfma_kernel') if cb.stem_mfma(dtype, Q) else kernel
+
+
+def _stem_kernels(N, H, W, dtype, ld=40, ld_dy=32, data='rand'):
+    """forward (training and eval form), BatchNorm partial sums and weight gradient (plain and accumulating) of one geometry, each
+    element against float64 under the bounds counted in conv_bounds.py (stem_u8_fwd / stem_affine / stem_u8_wgrad).
+    ld, ld_dy: row strides of y and dy; their pad columns hold NaN: y's must stay NaN, dy's must not be read.
+    data: 'rand' random pixels and 0.2 * randn taps; '255' all pixels 255 and taps of one sign (the largest magnitudes);
+    '0' all pixels 0 (every output of a channel is the same bias constant; the weight gradient is b_c * sum dy)."""
     from ifcb_classifier_amd import _lib
     from ifcb_classifier_amd._lib import ConvDesc
     ctx = _lib.Context(0)
     st = _lib.cur_stream()
     tdt = torch.bfloat16 if dtype == 'bf16' else torch.float32
     cdt = _lib.BF16 if dtype == 'bf16' else _lib.F32
-    P, Q, K, LD = (H - 3) // 2 + 1, (W - 3) // 2 + 1, 32, 40
+    P, Q, K, LD = (H - 3) // 2 + 1, (W - 3) // 2 + 1, 32, ld
+    mfma = cb.stem_mfma(dtype, Q)
     d = ConvDesc(N, H, W, 8, 8, K, 3, 3, 2, 2, 0, 0, P, Q, LD, 3, cdt)
     rows = ctx.lib.ifcbk_stem_u8_rows(C.byref(d))
-    assert rows == ((N * P + 7) // 8 if dtype == 'bf16' and Q >= 32 else (N * P * Q + 2047) // 2048)      # MFMA kernels: a block per 8 output rows
+    assert rows == cb.stem_rows(N, P, Q, dtype)                                        # MFMA kernels: a block per 8 output rows
     ctx.reserve(max(1 << 20, ctx.lib.ifcbk_stem_u8_wgrad_workspace(C.byref(d))))
     gen = torch.Generator(device='cuda').manual_seed(3)
     g = torch.randint(0, 256, (N, H, W), device='cuda', generator=gen, dtype=torch.uint8)
     w = torch.randn(K, 3, 3, 3, device='cuda', generator=gen) * 0.2                    # master layout [K][R][S][C]
+    if data == '255':
+        g.fill_(255)
+        w = w.abs() * torch.where(torch.arange(K, device='cuda') % 2 == 0, 1.0, -1.0)[:, None, None, None]
+    elif data == '0':
+        g.zero_()
     ab_host = _ab((0.485, 0.456, 0.406), (0.229, 0.224, 0.225), (0.458, 0.448, 0.45), (-0.03, -0.088, -0.188))
     ab = torch.tensor(ab_host, device='cuda', dtype=torch.float32)
-    x = torch.stack([ab[c].double() * g.double() + ab[3 + c].double() for c in range(3)], 1)          # [N,3,H,W] fp64
-    x.requires_grad_(False)
-    w64 = w.double().permute(0, 3, 1, 2).contiguous().requires_grad_(True)
-    ref = F.conv2d(x, w64, None, 2)                                                   # [N,32,P,Q]
-    ref_y = ref.permute(0, 2, 3, 1).detach()
+    ref_y, e = cb.stem_u8_fwd(g, w, ab, mfma)
+    name = 'stem %dx%dx%d %s ld %d/%d %s' % (N, H, W, dtype, ld, ld_dy, data)
+    fam = _family('stem_u8_fwd_kernel', dtype, Q)
 
     # ---- training forward: raw output + BatchNorm partial sums of the rounded outputs; the pad columns stay untouched
     yb = torch.full((N, P, Q, LD), float('nan'), device='cuda', dtype=tdt)
@@ -52,10 +65,10 @@ def test_stem_u8_kernels_vs_fp64_conv_of_the_three_affine_planes(N, H, W, dtype)
     torch.cuda.synchronize()
     y = yb[..., :K]
     assert torch.isnan(yb[..., K:].float()).all()
-    tol = 2.0 ** -8 if dtype == 'bf16' else 2e-6
-    assert ((y.double() - ref_y).abs() <= tol * ref_y.abs() + 1e-4).all(), (y.double() - ref_y).abs().max().item()
-    assert _rel(part[:, 0].double().sum(0), y.double().sum((0, 1, 2))) < 2e-6
-    assert _rel(part[:, 1].double().sum(0), (y.double() ** 2).sum((0, 1, 2))) < 2e-6
+    cb.check_e(name + ' fwd', y, ref_y, e, dtype, family=fam)
+    cb.check_bn_fwd_sums(name + ' partial', part, y, family=fam + ' sums')
+    if data == '0':
+        assert bool((y == y[0, 0, 0]).all())                                           # one bias constant per channel, everywhere
     yb2 = torch.full_like(yb, float('nan'))
     part2 = torch.full_like(part, float('nan'))
     ctx.call('ifcbk_stem_u8_fwd', C.byref(d), _lib.ptr(g), _lib.ptr(w), _lib.ptr(ab), _lib.ptr(yb2), _lib.ptr(part2), None, None, 0, st)
@@ -70,25 +83,75 @@ def test_stem_u8_kernels_vs_fp64_conv_of_the_three_affine_planes(N, H, W, dtype)
         ctx.call('ifcbk_stem_u8_fwd', C.byref(d), _lib.ptr(g), _lib.ptr(w), _lib.ptr(ab), _lib.ptr(ya), None, _lib.ptr(scale),
                  _lib.ptr(shift), relu, st)
         torch.cuda.synchronize()
-        want = ref_y * scale.double() + shift.double()
-        if relu:
-            want = want.clamp_min(0)
-        assert ((ya[..., :K].double() - want).abs() <= tol * want.abs() + 2e-4).all()
+        assert torch.isnan(ya[..., K:].float()).all()
+        want, e_lin = cb.stem_affine(ref_y, e, scale, shift, bool(relu))
+        cb.check_e(name + ' affine relu %d' % relu, ya[..., :K], want, e_lin, dtype, family=fam + ' affine')
 
-    # ---- weight gradient (master layout [K][R][S][3]), plain and accumulating
-    d2 = ConvDesc(N, H, W, 8, 8, K, 3, 3, 2, 2, 0, 0, P, Q, K, 3, cdt)
-    dy = torch.randn(N, P, Q, K, device='cuda', generator=gen).to(tdt)
-    ref.backward(dy.double().permute(0, 3, 1, 2))
-    ref_dw = w64.grad.permute(0, 2, 3, 1).contiguous()                                # [K][R][S][C]
+    if data == '255':
+        # the fp32 accumulator seen through the storage type: every output of a channel is the same value here, and shift = -fl32(ref)
+        # cancels it, so what is stored is the accumulation error itself (a bf16 store of the full value hides everything below 2^-9)
+        one, neg = torch.ones(K, device='cuda'), (-ref_y[0, 0, 0]).float().cuda()
+        ya = torch.full((N, P, Q, LD), float('nan'), device='cuda', dtype=tdt)
+        ctx.call('ifcbk_stem_u8_fwd', C.byref(d), _lib.ptr(g), _lib.ptr(w), _lib.ptr(ab), _lib.ptr(ya), None, _lib.ptr(one), _lib.ptr(neg), 0, st)
+        torch.cuda.synchronize()
+        want, e_lin = cb.stem_affine(ref_y, e, one, neg, False)
+        e_st = e_lin + 0.5 * cb.ulp(want.abs() + e_lin, dtype)                        # the store, counted here: no mismatch fraction
+        cb.check_e(name + ' accumulator', ya[..., :K].float(), want, e_st, 'fp32', family=fam + ' accumulator')
+
+    # ---- weight gradient (master layout [K][R][S][3]), plain and accumulating; dy rows ld_dy apart, NaN between them
+    d2 = ConvDesc(N, H, W, 8, 8, K, 3, 3, 2, 2, 0, 0, P, Q, ld_dy, 3, cdt)
+    dyb = torch.full((N, P, Q, ld_dy), float('nan'), device='cuda', dtype=tdt)
+    dyb[..., :K] = torch.randn(N, P, Q, K, device='cuda', generator=gen).to(tdt)
+    ref_dw, e_dw = cb.stem_u8_wgrad(g, dyb[..., :K], ab, mfma)
+    famw = _family('stem_u8_wgrad_kernel', dtype, Q) + ' + reduce'
     dw = torch.full((K, 3, 3, 3), float('nan'), device='cuda')
-    ctx.call('ifcbk_stem_u8_wgrad', C.byref(d2), _lib.ptr(g), _lib.ptr(dy), _lib.ptr(ab), _lib.ptr(dw), 0, st)
+    ctx.call('ifcbk_stem_u8_wgrad', C.byref(d2), _lib.ptr(g), _lib.ptr(dyb), _lib.ptr(ab), _lib.ptr(dw), 0, st)
     torch.cuda.synchronize()
-    assert _rel(dw, ref_dw) < 2e-5, _rel(dw, ref_dw)
+    cb.check_stem_wgrad(name + ' wgrad', dw, ref_dw, e_dw, family=famw)
     base = torch.randn(K, 3, 3, 3, device='cuda', generator=gen)
     dw2 = base.clone()
-    ctx.call('ifcbk_stem_u8_wgrad', C.byref(d2), _lib.ptr(g), _lib.ptr(dy), _lib.ptr(ab), _lib.ptr(dw2), 1, st)
+    ctx.call('ifcbk_stem_u8_wgrad', C.byref(d2), _lib.ptr(g), _lib.ptr(dyb), _lib.ptr(ab), _lib.ptr(dw2), 1, st)
     torch.cuda.synchronize()
     assert torch.equal(dw2, base + dw)
+    cb.check_stem_wgrad(name + ' wgrad +=', dw2, ref_dw, e_dw, old=base, family=famw)
+    return fam, famw
+
+
+STEM = [(3, 299, 299, 'bf16'), (2, 31, 37, 'bf16'), (5, 64, 64, 'fp32'), (1, 33, 9, 'fp32'), (40, 75, 75, 'bf16'), (2, 69, 67, 'bf16'),
+        (3, 90, 131, 'bf16'),
+        # Q = 31 / 32 / 33 / 64 (the stem_mfma switch, one full group, a last group of one new pixel, two full groups), W even and
+        # odd (the unread last column), N * P not a multiple of RB = 8, N = 1
+        (3, 21, 64, 'bf16'), (3, 21, 65, 'bf16'), (3, 22, 66, 'bf16'), (1, 23, 67, 'bf16'), (3, 21, 68, 'bf16'), (1, 9, 130, 'bf16'),
+        (2, 20, 129, 'fp32'),
+        # M = N * P * Q at 2047 / 2048 / 2049 (PIXB) and 255 / 256 / 257 (64 * UNR) for the vector kernels
+        (1, 47, 179, 'fp32'), (1, 65, 129, 'fp32'), (1, 7, 1367, 'fp32'), (1, 31, 35, 'fp32'), (1, 33, 33, 'bf16'), (1, 3, 515, 'fp32'),
+        (1, 4, 516, 'bf16')]
+
+
+@pytest.mark.parametrize('N,H,W,dtype', STEM)
+def test_stem_u8_kernels_vs_fp64_conv_of_the_three_affine_planes(N, H, W, dtype):
+    _stem_kernels(N, H, W, dtype)
+
+
+# (N, H, W, dtype, ld of y, ld of dy, data)
+STEM_EDGES = [(2, 31, 37, 'bf16', 64, 40, 'rand'), (3, 21, 67, 'bf16', 64, 40, 'rand'), (3, 21, 131, 'bf16', 40, 64, 'rand'),
+              (2, 20, 66, 'fp32', 64, 64, 'rand'), (1, 33, 9, 'fp32', 40, 40, 'rand'), (3, 90, 131, 'bf16', 32, 32, 'rand'),
+              (3, 45, 131, 'bf16', 40, 40, '255'), (2, 31, 37, 'bf16', 40, 32, '255'), (2, 33, 65, 'fp32', 40, 40, '255'),
+              (3, 45, 131, 'bf16', 40, 40, '0'), (2, 33, 65, 'fp32', 32, 40, '0'), (2, 31, 37, 'bf16', 40, 32, '0')]
+
+
+@pytest.mark.parametrize('N,H,W,dtype,ld,ld_dy,data', STEM_EDGES)
+def test_stem_u8_row_strides_and_extreme_pixels(N, H, W, dtype, ld, ld_dy, data):
+    _stem_kernels(N, H, W, dtype, ld, ld_dy, data)
+
+
+def stem_kernels_reached(cases):
+    """the kernels of conv_stem_u8.hip the case tables reach (test_op_inventory_cpu.py, test_gpu_conv_bounds.py::COUNTED)"""
+    out = set()
+    for c in cases:
+        Q = (c[2] - 3) // 2 + 1
+        out |= {_family('stem_u8_fwd_kernel', c[3], Q), _family('stem_u8_wgrad_kernel', c[3], Q), 'stem_u8_wgrad_reduce_kernel'}
+    return out
 
 
 def test_stem_u8_rows_beyond_the_2_gib_offset_of_the_output():

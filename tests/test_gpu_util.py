@@ -32,9 +32,15 @@ def _numpy_moments(planes, ch):
     return out
 
 
-@pytest.mark.parametrize('ch', [1, 3])
-@pytest.mark.parametrize('hw', [(299, 299), (224, 224), (1, 1), (37, 53)])
-@pytest.mark.parametrize('n', [1, 7, 300])
+# the cases of u8_moments_kernel (stats.hip), also read by test_op_inventory_cpu.py: (channels, (h, w), images)
+MOMENT_CH, MOMENT_HW, MOMENT_N = [1, 3], [(299, 299), (224, 224), (1, 1), (37, 53)], [1, 7, 300]
+MOMENT_EXTRA = [(2, (61, 47), 5), (4, (61, 47), 5)]           # test_u8_channel_moments_two_and_four_channels_and_all_255
+MOMENTS = [(ch, hw, n) for ch in MOMENT_CH for hw in MOMENT_HW for n in MOMENT_N] + MOMENT_EXTRA
+
+
+@pytest.mark.parametrize('ch', MOMENT_CH)
+@pytest.mark.parametrize('hw', MOMENT_HW)
+@pytest.mark.parametrize('n', MOMENT_N)
 def test_u8_channel_moments_exact(ctx, ch, hw, n):
     rng = np.random.default_rng(ch * 1000 + hw[0] + n)
     ppi = hw[0] * hw[1]
@@ -51,9 +57,9 @@ def test_u8_channel_moments_exact(ctx, ch, hw, n):
 
 def test_u8_channel_moments_two_and_four_channels_and_all_255(ctx):
     rng = np.random.default_rng(4)
-    for ch in (2, 4):
-        planes = rng.integers(0, 256, (5, 61 * 47 * ch), dtype=np.uint8)
-        assert np.array_equal(_moments(ctx, torch.from_numpy(planes).cuda(), 5, 61 * 47, ch), _numpy_moments(planes, ch))
+    for ch, (h, w), n in MOMENT_EXTRA:
+        planes = rng.integers(0, 256, (n, h * w * ch), dtype=np.uint8)
+        assert np.array_equal(_moments(ctx, torch.from_numpy(planes).cuda(), n, h * w, ch), _numpy_moments(planes, ch))
     full = torch.full((300, 299 * 299 * 3), 255, dtype=torch.uint8, device='cuda')
     got = _moments(ctx, full, 300, 299 * 299, 3)
     assert (got[..., 0] == 299 * 299 * 255).all() and (got[..., 1] == 299 * 299 * 255 * 255).all()

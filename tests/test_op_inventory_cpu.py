@@ -1,5 +1,6 @@
-"""Every kernel of bn.hip, pool_head.hip and plain.hip is reached by a case of tests/test_gpu_op_bounds.py, and every entry point of
-include/ifcbk.h is called by some test (CPU): a kernel or an entry point added later without a test fails here."""
+"""Every kernel of bn.hip, pool_head.hip and plain.hip is reached by a case of tests/test_gpu_op_bounds.py, every kernel of the input
+path (roi.hip, conv_stem_u8.hip, stats.hip) by a case of its own table, and every entry point of include/ifcbk.h is called by some
+test (CPU): a kernel or an entry point added later without a test fails here."""
 import glob
 import importlib
 import os
@@ -30,7 +31,35 @@ def _norm(s):
 
 def _kernels(fname):
     src = open(os.path.join(CSRC, fname)).read()
-    return set(re.findall(r'__global__\s+(?:__launch_bounds__\(\d+\)\s+)?void\s+(\w+)\s*\(', src))
+    return set(re.findall(r'__global__\s+(?:__launch_bounds__\(\w+\)\s+)?void\s+(\w+)\s*\(', src))
+
+
+def _stem(kernel):
+    return lambda c: kernel in importlib.import_module('test_gpu_stem_u8').stem_kernels_reached([c])
+
+
+def _roi(prefix):
+    return lambda c: any(p.startswith(prefix) for p in importlib.import_module('roi_bounds').paths(c))
+
+
+_MFMA = 'static bool stem_mfma(const ifcbk_conv_desc* d) { return d->dtype == IFCBK_BF16 && d->Q >= 32; }'
+# the input path: kernel -> (file, module holding the case table, table, reaches(case), dispatch condition quoted from the file).
+# roi_resize_kernel's three arithmetic paths have a predicate and a quoted condition each in roi_bounds.PATHS (test_roi_paths_cpu.py).
+INPUT_KERNELS = {
+    'roi_coeffs_kernel': ('roi.hip', 'roi_bounds', 'ROI', lambda c: True, 'hipLaunchKernelGGL(roi_coeffs_kernel, dim3(cdiv(nco, 256))'),
+    'roi_resize3_kernel': ('roi.hip', 'roi_bounds', 'ROI', _roi('roi_resize3_kernel'), 'if (d->in_channels == 1 && kmax == 3 && d->S <= 320)'),
+    'roi_resize_kernel': ('roi.hip', 'roi_bounds', 'ROI', _roi('roi_resize_kernel'), 'else hipLaunchKernelGGL(roi_resize_kernel,'),
+    'stem_u8_fwd_kernel': ('conv_stem_u8.hip', 'test_gpu_stem_u8', 'STEM', _stem('stem_u8_fwd_kernel'),
+                           'else hipLaunchKernelGGL((stem_u8_fwd_kernel<bf16_t, false>), grid, blk, 0, st, a);'),
+    'stem_u8_fwd_mfma_kernel': ('conv_stem_u8.hip', 'test_gpu_stem_u8', 'STEM', _stem('stem_u8_fwd_mfma_kernel'), _MFMA),
+    'stem_u8_wgrad_kernel': ('conv_stem_u8.hip', 'test_gpu_stem_u8', 'STEM', _stem('stem_u8_wgrad_kernel'),
+                             'else hipLaunchKernelGGL(stem_u8_wgrad_kernel<bf16_t>, dim3(nblk), dim3(256), 0, st, a);'),
+    'stem_u8_wgrad_mfma_kernel': ('conv_stem_u8.hip', 'test_gpu_stem_u8', 'STEM', _stem('stem_u8_wgrad_mfma_kernel'),
+                                  'else if (stem_mfma(d)) hipLaunchKernelGGL(stem_u8_wgrad_mfma_kernel,'),
+    'stem_u8_wgrad_reduce_kernel': ('conv_stem_u8.hip', 'test_gpu_stem_u8', 'STEM', _stem('stem_u8_wgrad_reduce_kernel'),
+                                    'hipLaunchKernelGGL(stem_u8_wgrad_reduce_kernel, dim3(K1), dim3(640), 0, st, (const float*)ctx->ws, nblk, ab, dw, accumulate);'),
+    'u8_moments_kernel': ('stats.hip', 'test_gpu_util', 'MOMENTS', lambda c: 1 <= c[0] <= 4, 'if (channels < 1 || channels > 4)'),
+}
 
 
 def test_every_kernel_has_cases_and_a_quoted_dispatch_condition():
@@ -45,6 +74,24 @@ def test_every_kernel_has_cases_and_a_quoted_dispatch_condition():
         assert any(reaches(c) for c in cases), '%s: no case of %s reaches it (%s)' % (name, table, cond)
         src = _norm(open(os.path.join(CSRC, fname)).read()) + _norm(open(os.path.join(ROOT, 'include', 'ifcbk.h')).read())
         assert _norm(cond) in src, '%s: the dispatch condition %r is no longer in the source' % (name, cond)
+
+
+def test_every_input_path_kernel_has_cases_and_a_quoted_dispatch_condition():
+    files = ('roi.hip', 'conv_stem_u8.hip', 'stats.hip')
+    found = {k: f for f in files for k in _kernels(f)}
+    assert sorted(found) == sorted(INPUT_KERNELS), (sorted(set(found) - set(INPUT_KERNELS)), sorted(set(INPUT_KERNELS) - set(found)))
+    for name, (fname, module, table, reaches, cond) in INPUT_KERNELS.items():
+        assert found[name] == fname, name
+        cases = getattr(importlib.import_module(module), table)
+        assert isinstance(cases, list) and cases, table
+        assert any(reaches(c) for c in cases), '%s: no case of %s.%s reaches it (%s)' % (name, module, table, cond)
+        assert _norm(cond) in _norm(open(os.path.join(CSRC, fname)).read()), '%s: the dispatch condition %r is no longer in the source' % (name, cond)
+    # every channel count the moments kernel is instantiated for
+    assert {c[0] for c in importlib.import_module('test_gpu_util').MOMENTS} == {1, 2, 3, 4}
+    # the conv inventory's exemptions name the same five stem kernels
+    counted = importlib.import_module('test_gpu_conv_bounds').COUNTED
+    assert {k for k in INPUT_KERNELS if k.startswith('stem_u8')} <= set(counted)
+    assert not [v for v in counted.values() if 'norm' in v]
 
 
 def test_every_entry_point_is_called_by_a_test():
