@@ -27,14 +27,15 @@ OK, EINVAL, EHIP, ENOMEM, EUNSUPPORTED = 0, -1, -2, -3, -4        # include/ifcb
  OP_WEIGHT_PACK_MULTI, OP_CONV_WGRAD_SEG, OP_BN_APPLY_MAXPOOL, OP_BN_BWD_MAXPOOL, OP_CONV_DGRAD_BNSTAT,
  OP_BN_BWD_PARTIALS, OP_BN_STATS, OP_AVGPOOL_AFFINE, OP_CONV_FWD_AFFINE_SEG, OP_SGD, OP_RETIRED_31,
  OP_BIAS_RELU_BWD, OP_DROPOUT, OP_FLATTEN_CHW, OP_STEM_U8_FWD, OP_STEM_U8_WGRAD, OP_CONV_FWD_AFFINE_MAXPOOL,
- OP_STEP_COUNTERS, OP_CONV_WGRAD_GROUP) = range(1, 40)
+ OP_STEP_COUNTERS, OP_CONV_WGRAD_GROUP, OP_SOFTMAX_XENT_W) = range(1, 41)
 
 OP_NAMES = {1: 'conv_fwd', 2: 'conv_dgrad', 3: 'conv_wgrad', 4: 'weight_pack', 5: 'bn_finalize', 6: 'bn_apply',
             7: 'bn_bwd', 8: 'maxpool_fwd', 9: 'maxpool_bwd', 10: 'avgpool_fwd', 11: 'avgpool_bwd', 12: 'head_fwd',
             13: 'head_bwd', 14: 'softmax_xent', 15: 'softmax', 16: 'adam', 17: 'memset', 18: 'copy2d',
             19: 'dropout_mask', 20: 'conv_fwd_affine', 21: 'weight_pack_multi', 22: 'conv_wgrad', 23: 'bn_apply_maxpool',
             24: 'bn_bwd_maxpool', 25: 'conv_dgrad', 26: 'bn_bwd', 27: 'bn_stats', 28: 'avgpool_fwd', 29: 'conv_fwd_affine', 30: 'sgd', 31: 'retired',
-            32: 'bias_relu_bwd', 33: 'dropout', 34: 'flatten_chw', 35: 'conv_fwd', 36: 'conv_wgrad', 37: 'conv_fwd_affine', 38: 'step_counters', 39: 'conv_wgrad'}
+            32: 'bias_relu_bwd', 33: 'dropout', 34: 'flatten_chw', 35: 'conv_fwd', 36: 'conv_wgrad', 37: 'conv_fwd_affine', 38: 'step_counters', 39: 'conv_wgrad',
+            40: 'softmax_xent_w'}
 
 
 class ConvDesc(C.Structure):
@@ -140,6 +141,7 @@ _PROTOS = {
     'ifcbk_flatten_chw': (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp]),
     'ifcbk_softmax_xent': (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _i, _vp, _vp]),
     'ifcbk_softmax': (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    'ifcbk_softmax_xent_w': (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _vp, _i, _vp, _vp]),
     'ifcbk_step_counters': (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     'ifcbk_adam_flat': (_i, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _f, _f, _f, _f, _f, _i, _f, _vp]),
     'ifcbk_sgd_flat': (_i, [_vp, _vp, _vp, _vp, C.c_int64, _f, _f, _f, _f, _vp]),

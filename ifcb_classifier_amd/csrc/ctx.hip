@@ -207,6 +207,9 @@ static int run_one(ifcbk_ctx* c, const ifcbk_op* o, void* st) {
         case IFCBK_OP_SOFTMAX_XENT:
             return ifcbk_softmax_xent(c, (const float*)p[0], (const int64_t*)p[1], (int)o->i[0], (int)o->i[1], o->f[0],
                                       (float*)p[2], acc, (float*)p[3], st);
+        case IFCBK_OP_SOFTMAX_XENT_W:
+            return ifcbk_softmax_xent_w(c, (const float*)p[0], (const int64_t*)p[1], (const float*)p[4], (int)o->i[0], (int)o->i[1], o->f[0],
+                                        (float*)p[2], acc, (float*)p[3], st);
         case IFCBK_OP_SOFTMAX: return ifcbk_softmax(c, (const float*)p[0], (int)o->i[0], (int)o->i[1], (float*)p[1], st);
         case IFCBK_OP_ADAM:
             return ifcbk_adam_flat(c, (float*)p[0], (const float*)p[1], (float*)p[2], (float*)p[3], o->i[0], o->f[0], o->f[1],

@@ -180,7 +180,7 @@ class Engine:
         return max(1, _index_bytes() // per_img)
 
     def __init__(self, net, device=0, max_batch=32, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, dtype='bf16', optimizer='adam',
-                 momentum=0.0, plan_only=False, train_batch=None, dp_world=None):
+                 momentum=0.0, plan_only=False, train_batch=None, dp_world=None, class_weights=None, weight_decay=0.0):
         # dp_world: world size of the data-parallel job this replica belongs to (None: WORLD_SIZE of the launcher, else an
         # initialised torch.distributed group, else 1) -- it picks the program-lane default, and train_step_ddp checks it
         self._dp_world_arg = None if dp_world is None else int(dp_world)
@@ -192,6 +192,18 @@ class Engine:
         if str(optimizer).lower() not in ('adam', 'sgd'):
             raise ValueError("optimizer must be 'adam' (the reference's only behaviour, neuston_models.py:63-64) or 'sgd'")
         self.optimizer, self.momentum = str(optimizer).lower(), float(momentum)
+        # additive options (TRAIN --weight-decay / --class-norm; upstream has neither): torch's L2 form g + wd * p in the fused
+        # Adam / SGD kernels, and per-class weights of the loss (nn.CrossEntropyLoss(weight=...)); None / 0.0: upstream's behaviour
+        self.weight_decay = float(weight_decay or 0.0)
+        if self.weight_decay < 0:
+            raise ValueError('weight_decay must be >= 0')
+        if class_weights is not None:
+            class_weights = [float(w) for w in (class_weights.tolist() if hasattr(class_weights, 'tolist') else class_weights)]
+            if len(class_weights) != net.NC:
+                raise ValueError('class_weights: %d values for %d classes' % (len(class_weights), net.NC))
+            if not all(math.isfinite(w) and w >= 0 for w in class_weights) or not any(class_weights):
+                raise ValueError('class_weights must be finite, non-negative and not all zero')
+        self._class_weights_arg = class_weights
         self.net = net
         if dtype not in ('bf16', 'fp32'):
             raise ValueError("dtype must be 'bf16' (performance) or 'fp32' (parity mode)")
@@ -582,6 +594,8 @@ class Engine:
         self.ev_ready, self.ev_free, self.prefetched = [None, None], [None, None], None
         self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
         self.loss_sum = torch.zeros(1, dtype=torch.float32, device=dev)
+        # per-class loss weights: one fp32 [NC] tensor, read by the loss ops only (never written by a program)
+        self.class_weight = None if self._class_weights_arg is None else torch.tensor(self._class_weights_arg, dtype=torch.float32, device=dev)
         # workspace: wgrad split-K slabs / bn_bwd partials
         ws = 1 << 20
         for n in self.convs:
@@ -1389,14 +1403,17 @@ class Engine:
         lossl = OpList()
         main = [h for h in self.heads if not h.aux][0]
         auxh = [h for h in self.heads if h.aux]
-        lossl.add(_lib.OP_SOFTMAX_XENT, 'loss', p=(_vp(main.logits), _vp(self.target), _vp(self.loss), _vp(main.dlogits)),
+        # with class weights (TRAIN --class-norm): the same three ops as OP_SOFTMAX_XENT_W, the weight tensor as a fifth operand.
+        # Loss ops carry no lane annotation: they are full barriers on lane 0, so the read-only weight tensor needs no resource entry
+        xent, cw = (_lib.OP_SOFTMAX_XENT, ()) if self.class_weight is None else (_lib.OP_SOFTMAX_XENT_W, (_vp(self.class_weight),))
+        lossl.add(xent, 'loss', p=(_vp(main.logits), _vp(self.target), _vp(self.loss), _vp(main.dlogits)) + cw,
                   i=(N, net.NC), f=(1.0,))
         for h in auxh:
-            lossl.add(_lib.OP_SOFTMAX_XENT, 'loss_aux', p=(_vp(h.logits), _vp(self.target), _vp(self.loss), _vp(h.dlogits)),
+            lossl.add(xent, 'loss_aux', p=(_vp(h.logits), _vp(self.target), _vp(self.loss), _vp(h.dlogits)) + cw,
                       i=(N, net.NC), f=(0.4,), flags=1)
         pl.loss = Program(lossl)
         evl = OpList()
-        evl.add(_lib.OP_SOFTMAX_XENT, 'val_loss', p=(_vp(main.logits), _vp(self.target), _vp(self.loss), None), i=(N, net.NC), f=(1.0,))
+        evl.add(xent, 'val_loss', p=(_vp(main.logits), _vp(self.target), _vp(self.loss), None) + cw, i=(N, net.NC), f=(1.0,))
         pl.eval_loss = Program(evl)
         sm = OpList()
         sm.add(_lib.OP_SOFTMAX, 'softmax', p=(_vp(main.logits), _vp(self.probs)), i=(N, net.NC))
@@ -1405,10 +1422,10 @@ class Engine:
         if self.optimizer == 'sgd':
             # additive option (north_star "SGD/Adam step"; upstream only has Adam): torch.optim.SGD's update, momentum buffer = M
             opt.add(_lib.OP_SGD, 'sgd', p=(_vp(self.P), _vp(self.G), _vp(self.M) if self.momentum else None),
-                    i=(self.nparam_padded, 1), f=(self.lr, self.momentum, 0.0, 1.0))
+                    i=(self.nparam_padded, 1), f=(self.lr, self.momentum, self.weight_decay, 1.0))
         else:
             opt.add(_lib.OP_ADAM, 'adam', p=(_vp(self.P), _vp(self.G), _vp(self.M), _vp(self.V)),
-                    i=(self.nparam_padded, 1), f=(self.lr, self.betas[0], self.betas[1], self.eps, 0.0, 1.0))
+                    i=(self.nparam_padded, 1), f=(self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, 1.0))
         pl.adam = Program(opt)
         # the step's bookkeeping in the step's own op table: num_batches_tracked += 1 of every BatchNorm, loss_sum += loss
         cnt = OpList()

@@ -259,13 +259,18 @@ class NeustonModel(nn.Module):
         if isinstance(hparams, dict):
             hparams = argparse.Namespace(**hparams)
         self.hparams = hparams
-        self.criterion = nn.CrossEntropyLoss()
         mb = max_batch or getattr(hparams, 'batch_size', None) or 32
         opt = str(getattr(hparams, 'optimizer', None) or 'Adam').lower()
+        # additive (TRAIN --class-norm / --weight-decay): per-class loss weights and L2 weight decay; absent = upstream's behaviour
+        cw = getattr(hparams, 'class_weights', None)
         self.model = get_namebrand_model(hparams.MODEL, len(hparams.classes), hparams.pretrained, device, mb,
                                          getattr(hparams, 'precision', 'bf16') or 'bf16', optimizer=opt,
                                          lr=float(getattr(hparams, 'learning_rate', None) or 0.001),
-                                         momentum=float(getattr(hparams, 'momentum', None) or 0.0), train_batch=train_batch)
+                                         momentum=float(getattr(hparams, 'momentum', None) or 0.0), train_batch=train_batch,
+                                         class_weights=cw, weight_decay=float(getattr(hparams, 'weight_decay', None) or 0.0))
+        # what upstream would have written at neuston_models.py:55; the engine's fused loss ops compute the same weighted mean
+        eng = self.model.engine
+        self.criterion = nn.CrossEntropyLoss() if cw is None else nn.CrossEntropyLoss(weight=eng.class_weight.clone())
         self.best_val_loss = np.inf
         self.best_epoch = 0
         self.agg_train_loss = 0.0
@@ -276,9 +281,20 @@ class NeustonModel(nn.Module):
         eng = self.model.engine
         if eng.optimizer == 'sgd':            # additive option; the reference's only behaviour is Adam(lr=0.001) (:63-64)
             from torch.optim import SGD
-            return SGD(self.parameters(), lr=eng.lr, momentum=eng.momentum)
+            return SGD(self.parameters(), lr=eng.lr, momentum=eng.momentum, weight_decay=eng.weight_decay)
         from torch.optim import Adam
-        return Adam(self.parameters(), lr=eng.lr)
+        return Adam(self.parameters(), lr=eng.lr, weight_decay=eng.weight_decay)
+
+    def load_state_dict(self, state_dict, strict=True):
+        """``criterion.weight`` (the buffer of a weighted nn.CrossEntropyLoss, TRAIN --class-norm) is derived from the hyper-parameters:
+        a state_dict may carry it or not, whatever this model was built with -- the model's own weights stay in force."""
+        sd = dict(state_dict)
+        own = self.criterion.weight
+        if own is None:
+            sd.pop('criterion.weight', None)
+        else:
+            sd['criterion.weight'] = own          # (the engine's loss ops hold the same values)
+        return super().load_state_dict(sd, strict)
 
     def forward(self, inputs):
         return self.model(inputs)
@@ -497,9 +513,9 @@ class NeustonModel(nn.Module):
             else:
                 state[i] = dict(step=eng.step_count, exp_avg=view(eng.M), exp_avg_sq=view(eng.V))
         if eng.optimizer == 'sgd':
-            group = dict(lr=eng.lr, momentum=eng.momentum, dampening=0, weight_decay=0, nesterov=False, params=ids)
+            group = dict(lr=eng.lr, momentum=eng.momentum, dampening=0, weight_decay=eng.weight_decay or 0, nesterov=False, params=ids)
         else:
-            group = dict(lr=eng.lr, betas=tuple(eng.betas), eps=eng.eps, weight_decay=0, amsgrad=False, params=ids)
+            group = dict(lr=eng.lr, betas=tuple(eng.betas), eps=eng.eps, weight_decay=eng.weight_decay or 0, amsgrad=False, params=ids)
         return dict(state=state, param_groups=[group])
 
     def checkpoint_dict(self, epoch=0, global_step=0):

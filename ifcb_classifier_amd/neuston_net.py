@@ -37,6 +37,30 @@ def seed_everything(seed=None):
     return seed
 
 
+def class_norm_weights(counts, power):
+    """``--class-norm POWER``: per-class loss weights w_c = Z * n_c ** -POWER from the per-class counts n_c of the training split, with
+    Z = sum n_c / sum n_c ** (1 - POWER), so that sum_c n_c * w_c == sum_c n_c: the mean weight over the training samples is 1.
+    POWER = 1 is the "balanced" weighting N / (C * n_c), POWER = 0 all ones.  Computed in float64, rounded once to float32; returned
+    as a list of python floats holding exactly those float32 values.  A class without a training sample gets weight 0 (it cannot
+    occur as a training target) and stays out of both sums."""
+    power = float(power)
+    if power < 0:
+        raise ValueError('class-norm POWER must be >= 0')
+    n = [float(c) for c in counts]
+    if not any(c > 0 for c in n):
+        raise ValueError('class-norm: the training split is empty')
+    z = sum(n) / sum(c ** (1.0 - power) for c in n if c > 0)
+    w64 = [z * c ** -power if c > 0 else 0.0 for c in n]
+    return [float(v) for v in np.asarray(w64, dtype=np.float64).astype(np.float32)]
+
+
+def _class_norm_power(text):
+    v = float(text)
+    if not v >= 0:
+        raise argparse.ArgumentTypeError('POWER must be >= 0, got %r' % text)
+    return v
+
+
 def _dist():
     import torch.distributed as dist
     if int(os.environ.get('WORLD_SIZE', 1)) > 1:
@@ -296,6 +320,14 @@ def do_training(args):
     training_dataset, validation_dataset = get_trainval_datasets(args)
     assert training_dataset.classes == validation_dataset.classes
     args.classes = training_dataset.classes
+    args.class_weights = None
+    if args.class_norm is not None:
+        # counts of the whole training split (before any data-parallel sharding: every rank holds the same weights), args.classes order
+        args.class_weights = class_norm_weights(training_dataset.count_perclass, args.class_norm)
+        lo = min(range(len(args.classes)), key=lambda c: args.class_weights[c])
+        hi = max(range(len(args.classes)), key=lambda c: args.class_weights[c])
+        print('Class-norm POWER {:g}: loss weights from {:.4g} ({}) to {:.4g} ({})'.format(
+            args.class_norm, args.class_weights[lo], args.classes[lo], args.class_weights[hi], args.classes[hi]))
     dist, rank, world = _dist()
     if rank == 0:
         with open(os.path.join(args.outdir, 'training_images.list'), 'w') as f:
@@ -530,6 +562,8 @@ def argparse_nn_train(train_subparser):
     optim.add_argument('--optimizer', default='Adam', choices=['Adam', 'SGD'], help='Select an optimizer. Default is Adam')
     optim.add_argument('--learning-rate', default=0.001, type=float, help='Set a learning rate. Default is 0.001')
     optim.add_argument('--momentum', default=0.0, type=float, help='SGD momentum. Default is 0')
+    optim.add_argument('--weight-decay', default=0.0, type=float, help='L2 weight decay of every parameter, as torch.optim.Adam/SGD(weight_decay=WD) (not AdamW). Default is 0')
+    optim.add_argument('--class-norm', metavar='POWER', nargs='?', const=1.0, type=_class_norm_power, default=None, help='Bias results to emphasize smaller classes: weight the loss of class c by n_c^-POWER (n_c: training images of the class), scaled to a mean weight of 1 per training image. POWER defaults to 1 ("balanced"); 0 weights all classes equally. Default (unset) is the unweighted loss')
     meta = t.add_argument_group(title='Metadata and Annotations')
     meta.add_argument('--dataset-id', help='Associate a dataset id label with this model')
     meta.add_argument('--notes', help='Add any kind of note to the trained model.')

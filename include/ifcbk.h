@@ -219,6 +219,13 @@ IFCBK_API int ifcbk_dropout_mask(ifcbk_ctx*, uint8_t* mask, int64_t n, float p, 
 IFCBK_API int ifcbk_softmax_xent(ifcbk_ctx*, const float* logits, const int64_t* target, int N, int NC, float weight,
                        float* loss_out, int loss_accumulate, float* dlogits, void* stream);
 IFCBK_API int ifcbk_softmax(ifcbk_ctx*, const float* logits, int N, int NC, float* probs, void* stream);
+/* the same with per-class weights (TRAIN --class-norm): nn.CrossEntropyLoss(weight=class_weight), mean reduction, what upstream
+ * would have written at neuston_models.py:55.  W = sum_i class_weight[target_i];
+ * loss_out[0] (+)= weight * sum_i class_weight[target_i] CE(logits_i, target_i) / W;
+ * dlogits_i = weight * class_weight[target_i] / W * (softmax_i - onehot_i).  class_weight: NC floats, NULL is IFCBK_EINVAL (the
+ * unweighted loss keeps its own entry point).  All-ones weights give ifcbk_softmax_xent's results bit for bit.               */
+IFCBK_API int ifcbk_softmax_xent_w(ifcbk_ctx*, const float* logits, const int64_t* target, const float* class_weight, int N, int NC,
+                         float weight, float* loss_out, int loss_accumulate, float* dlogits /*nullable*/, void* stream);
 /* the bookkeeping of one fused train step, in the step's own op table (no framework kernel between the first and the last
  * launch of a step): num_batches_tracked[0..n) += 1 of every BatchNorm ([PL]/torch: nn.BatchNorm2d.forward in training) and
  * loss_sum += loss (the reference's train_loss is the SUM of the batch losses, neuston_models.py:85).  Either part may be NULL. */
@@ -372,8 +379,9 @@ enum {
     IFCBK_OP_STEM_U8_WGRAD,  /* p: g, dy, ab, dw; flags bit 0 accumulate                                                           */
     IFCBK_OP_CONV_FWD_AFFINE_MAXPOOL, /* p: x, w, y_pooled, scale, shift; i[0] = ld of y_pooled; flags bit 2 relu                  */
     IFCBK_OP_STEP_COUNTERS,  /* p: num_batches_tracked (i64, nullable), loss_sum (nullable), loss; i[0] = number of BatchNorms      */
-    IFCBK_OP_CONV_WGRAD_GROUP /* p[0]: HOST array of i[0] ifcbk_wgrad_item entries, kept alive by the caller; p[1..]: the members' dw again
+    IFCBK_OP_CONV_WGRAD_GROUP,/* p[0]: HOST array of i[0] ifcbk_wgrad_item entries, kept alive by the caller; p[1..]: the members' dw again
                                * (what the data-parallel bucket planner reads); flags bit 0 accumulate                            */
+    IFCBK_OP_SOFTMAX_XENT_W  /* p: logits, target, loss, dlogits (nullable), class_weight; i: N, NC; f[0] = weight; flags bit 0 accumulate */
 };
 typedef struct {
     ifcbk_conv_desc d;
