@@ -185,6 +185,7 @@ int ifcbk_conv_flat_launch(ifcbk_ctx* ctx, void* conv_args, int N, hipStream_t s
 int ifcbk_conv_slab_plan(int dtype, int N, int H, int W, int C, int K, int R, int S, int ph, int pw, int P, int Q);
 int ifcbk_conv_slab_launch(ifcbk_ctx* ctx, void* conv_args, int N, hipStream_t st);
 int ifcbk_conv_fwd_nt(int K, int M);
+int ifcbk_conv_f32_nt(int K);                                  // conv_igemm<float, NT, 2, 2, MODE>: the fp32 mode's column tile
 bool ifcbk_conv_ws_shape(int dtype, int M, int K, int Kg);     // the persistent warp-specialised kernel serves this GEMM shape
 int ifcbk_conv_fwd_wm(int M, int K);
 void ifcbk_conv_wgrad_shape(const ifcbk_conv_desc* d, int* mt, int* cols);

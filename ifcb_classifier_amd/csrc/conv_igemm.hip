@@ -632,6 +632,8 @@ int ifcbk_num_cus() { return num_cus(); }
 
 int ifcbk_conv_fwd_nt(int K, int M) { return pick_nt(K, pick_wm(M, K) == 4 ? 5 : 6); }
 
+int ifcbk_conv_f32_nt(int K) { return pick_nt(K, 4); }
+
 int ifcbk_conv_fwd_wm(int M, int K) { return pick_wm(M, K); }
 
 bool ifcbk_conv_ws_shape(int dtype, int M, int K, int Kg) { return ws_shape_ok(dtype, M, K, Kg); }

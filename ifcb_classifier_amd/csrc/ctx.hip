@@ -492,6 +492,7 @@ extern "C" int ifcbk_op_kernel(const ifcbk_op* o, char* name, size_t cap) {
         case IFCBK_OP_CONV_FWD_AFFINE_SEG: {
             const ifcbk_conv_desc& d = o->u.conv;
             int bmt = 0, btn = 0;
+            if (d.dtype == IFCBK_F32) { snprintf(name, cap, "conv_igemm<float, %d, 2, 2, 4>", ifcbk_conv_f32_nt(d.K)); break; }
             if (ifcbk_conv_big_plan(d.dtype, d.N * d.P * d.Q, d.K, d.R * d.S * d.C, &bmt, &btn))
                 snprintf(name, cap, "conv_pp2<%d, %d, %d, 4>", btn, bmt, bmt == 10 ? 4 : bmt / 2);
             else
@@ -502,6 +503,8 @@ extern "C" int ifcbk_op_kernel(const ifcbk_op* o, char* name, size_t cap) {
             const ifcbk_conv_desc& d = o->u.conv;
             int wm = ifcbk_conv_fwd_wm(d.N * d.P * d.Q, d.K);
             int bmt = 0, btn = 0;
+            // the fp32 parity mode has one kernel family: conv_igemm<float> with 128-pixel tiles and at most 128 columns
+            if (d.dtype == IFCBK_F32) { snprintf(name, cap, "conv_igemm<float, %d, 2, 2, 0>", ifcbk_conv_f32_nt(d.K)); break; }
             const bool rows = ifcbk_conv_rows_ok(d.dtype, d.C, d.K, d.R, d.S, d.stride_h, d.stride_w, d.pad_h, d.pad_w, d.Q) && !(o->kind == IFCBK_OP_CONV_FWD_AFFINE && o->p[5]);
             if (!rows && d.stride_h == 1 && d.stride_w == 1 && !(o->kind == IFCBK_OP_CONV_FWD_AFFINE && o->p[5]) &&
                 ifcbk_conv_flat_rows(d.dtype, d.N, d.H, d.W, d.C, d.K, d.R, d.S, d.pad_h, d.pad_w, d.P, d.Q)) {
@@ -567,6 +570,11 @@ extern "C" int ifcbk_op_kernel(const ifcbk_op* o, char* name, size_t cap) {
                     break;
                 }
                 const bool classes = d.stride_h == 2 && d.stride_w == 2 && d.R >= 2 && d.S >= 2 && d.H >= 2 && d.W >= 2;
+                if (d.dtype == IFCBK_F32) {
+                    snprintf(name, cap, "conv_igemm<float, %d, 2, 2, %d>", ifcbk_conv_f32_nt(d.C),
+                             o->kind == IFCBK_OP_CONV_DGRAD_BNSTAT ? 3 : classes ? 2 : (s2 ? 1 : 0));
+                    break;
+                }
                 snprintf(name, cap, "conv_igemm<unsigned short, %d, %d, %d, %d>", ifcbk_conv_fwd_nt(d.C, classes ? d.N * ((d.H + 1) / 2) * ((d.W + 1) / 2) : d.N * d.H * d.W), wm, wm == 4 ? 3 : 2,
                          o->kind == IFCBK_OP_CONV_DGRAD_BNSTAT ? 3 : classes ? 2 : (s2 ? 1 : 0));
             }

@@ -427,7 +427,8 @@ typedef struct ifcbk_graph ifcbk_graph;
 IFCBK_API int ifcbk_program_capture(ifcbk_ctx*, const ifcbk_op* ops, int n, ifcbk_graph** out);
 IFCBK_API int ifcbk_graph_launch(ifcbk_ctx*, ifcbk_graph*, void* stream);
 IFCBK_API int ifcbk_graph_destroy(ifcbk_ctx*, ifcbk_graph*);
-/* name of the (dominant) device kernel an op launches, e.g. "conv_igemm_bf16<4>" (as rocprofv3 prints it
+/* name of the (dominant) device kernel an op launches, e.g. "conv_igemm<unsigned short, 4, 2, 2, 0>" for a bf16
+ * descriptor and "conv_igemm<float, 2, 2, 2, 0>" for an fp32 one (as rocprofv3 prints it
  * inside its mangled/demangled symbol); returns 0 and "" for ops without a compute kernel               */
 IFCBK_API int ifcbk_op_kernel(const ifcbk_op* op, char* name, size_t cap);
 /* algorithmic work of one op: flops (MAC*2 of conv/FC only) and minimum HBM bytes                   */

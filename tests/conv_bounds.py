@@ -22,6 +22,8 @@ absolute values) and u = 2^-24 (fp32 unit roundoff):
   staged in LDS in that type): one rounding for each operation, so a bf16 accumulate also allows 1/2 ulp_bf16 of the contribution.
 * Eval affine epilogue act(scale * acc + shift [+ res]): the conv result is rounded to the storage type first (the same staging),
   then the multiply-add and the residual add are one fp32 rounding each, the ReLU is 1-Lipschitz, the store rounds once more.
+  In fp32 storage (check_affine(out='f32')) the same terms hold with 1/2 ulp_f32 for the staged conv value and for the store (the
+  staging does not round an fp32 accumulator; the term stays as a margin) and there is no mismatch fraction, as in check().
 
 Bf16 outputs also get a sensitivity check, which the worst-case bound is too loose to replace: the fraction of elements where
 y != rne_bf16(y64) must be at most 1 %.  One fp32 accumulation rounded once lands near 1e-3; a bf16-rounded partial sum pushes it to
@@ -186,22 +188,26 @@ def check_e(name, got, want, e, out='bf16', alts=(), dims=('n', 'p', 'q', 'k'), 
     return _finish(name, family, got, want, (got - want).abs(), bound, frac, dims, raise_)
 
 
-def check_affine(name, got, ref, A, n, scale, shift, res=None, relu=False, dims=('n', 'p', 'q', 'k'), family=None, raise_=True):
-    """bf16 y = act(scale[k] * conv + shift[k] (+ res)), scale / shift fp32 per output channel (last axis), res the bf16 residual"""
+def check_affine(name, got, ref, A, n, scale, shift, res=None, relu=False, dims=('n', 'p', 'q', 'k'), family=None, raise_=True,
+                 out='bf16'):
+    """y = act(scale[k] * conv + shift[k] (+ res)) stored as `out` ('bf16' | 'f32'), scale / shift fp32 per output channel (last axis),
+    res the residual in the storage type"""
     got = got.detach().double().cpu()
     ref, A = ref.double(), A.double()
     s, b = scale.detach().double().cpu(), shift.detach().double().cpu()
     r = torch.zeros(()) if res is None else res.detach().double().cpu()
     e = 2.0 * gamma(torch.as_tensor(n, dtype=torch.float64) + 1) * A
-    e_raw = e + 0.5 * ulp_bf16(ref.abs() + e)                      # the conv value as staged in bf16
+    e_raw = e + 0.5 * ulp(ref.abs() + e, out)                         # the conv value as staged in the storage type
     lin = s * ref + b + r
     mag = s.abs() * (ref.abs() + e_raw) + b.abs() + r.abs()
     e_lin = s.abs() * e_raw + 2.0 * U * mag                           # multiply-add and residual add: one rounding each
     act = (lambda t: t.clamp_min(0)) if relu else (lambda t: t)
     want = act(lin)
-    bound = 0.5 * ulp_bf16(want.abs() + e_lin) + e_lin
-    alt = act(s * rne(ref, 'bf16') + b + r)
-    frac = float(((got != rne(want, 'bf16')) & (got != rne(alt, 'bf16'))).double().mean())
+    bound = 0.5 * ulp(want.abs() + e_lin, out) + e_lin
+    frac = None
+    if out == 'bf16':
+        alt = act(s * rne(ref, 'bf16') + b + r)
+        frac = float(((got != rne(want, 'bf16')) & (got != rne(alt, 'bf16'))).double().mean())
     return _finish(name, family, got, want, (got - want).abs(), bound, frac, dims, raise_)
 
 

@@ -334,3 +334,49 @@ def test_stem_wgrad_bound_rejects_a_missing_last_pixel_group_of_one_row(mfma):
     base = torch.randn(32, 3, 3, 3)
     assert cb.check_stem_wgrad('acc', base + good, ref, e, old=base).ratio < 1
     assert cb.check_stem_wgrad('acc twice', base + good + good, ref, e, old=base, raise_=False).nbad > 0
+
+
+# ------------------------------------------------------------------------------------------------------ the fp32 affine epilogue
+# conv_igemm<float> emulated on the CPU: the fp32 MFMA as a sequential fma chain over the reduction, then fmaf(acc, scale, shift), an
+# fp32 add of the residual, the ReLU; reduction lengths Cw * R * S of the fp32 table of test_gpu_conv_f32_bounds.py
+F32_AFFINE = [(12, 3, 3), (3, 3, 3), (64, 1, 1), (48, 1, 7), (24, 3, 3)]          # 108, 27, 64, 336, 216
+
+
+def _f32_affine_emulated(x, w, pad, scale, shift, res, drop=None):
+    N, C, H, W = x.shape
+    K, _, R, S = w.shape
+    cols = torch.nn.functional.unfold(x, (R, S), padding=pad).permute(0, 2, 1).reshape(-1, 1, C * R * S)      # [M, 1, n]
+    wr = w.reshape(1, K, -1).expand(cols.shape[0], K, -1).clone()
+    if drop is not None:
+        m, k = drop
+        wr[m, k, int((cols[m, 0] * wr[m, k]).abs().argmax())] = 0           # the largest product of one output element goes missing
+    acc = torch.zeros(cols.shape[0], K)
+    for i in range(cols.shape[-1]):
+        acc = _fma(cols[..., i], wr[..., i], acc)
+    P, Q = H + 2 * pad[0] - R + 1, W + 2 * pad[1] - S + 1
+    v = _fma(acc.reshape(N, P, Q, K), scale, shift)
+    return torch.relu(v + res)
+
+
+@pytest.mark.parametrize('C,R,S', F32_AFFINE)
+def test_f32_affine_bound_accepts_the_fma_chain_and_rejects_a_dropped_product(C, R, S):
+    g = torch.Generator().manual_seed(20 + C * R * S)
+    K, N, H, W = 8, 2, 5, 9
+    pad = (R // 2, S // 2)
+    x = torch.randn(N, C, H, W, generator=g)
+    w = torch.randn(K, C, R, S, generator=g) / (C * R * S) ** 0.5
+    scale, shift = torch.rand(K, generator=g) + 0.5, torch.randn(K, generator=g) * 0.3
+    res = torch.randn(N, H, W, K, generator=g)
+    ref, A, n = cb.fwd(x, w, 1, pad)
+    assert n == C * R * S
+    y = _f32_affine_emulated(x, w, pad, scale, shift, res)
+    r = cb.check_affine('f32 affine', y, ref, A, n, scale, shift, res, relu=True, out='f32')
+    assert r.ratio < 1.0 and r.frac is None
+    pre = scale.double() * ref + shift.double() + res.double()
+    m = int(pre[..., 3].flatten().argmax())                                 # an element the ReLU passes
+    bad = _f32_affine_emulated(x, w, pad, scale, shift, res, drop=(m, 3))
+    r = cb.check_affine('f32 affine', bad, ref, A, n, scale, shift, res, relu=True, out='f32', raise_=False)
+    assert r.nbad == 1 and r.ratio > 1.0, r
+    # the bf16 form of the same call is unchanged by the new parameter: an fp32 result is not a bf16 store
+    r = cb.check_affine('bf16 affine', _bf(y), ref, A, n, scale, shift, res, relu=True)
+    assert r.frac is not None

@@ -3,7 +3,7 @@ tile per block, and more tiles than CUs so that blocks loop), every epilogue mod
 2 parity class, 3 BN-backward sums, 4 segments) with Cw < C, N = 1 and M % 128 == 1, the weight-gradient kernels conv_wgrad_cols /
 conv_wgrad_rows, ifcbk_conv2d_wgrad_segments (bf16 and fp32 kernels) and ifcbk_weight_pack_multi.  Each case asserts through
 ifcbk_op_kernel which kernel ran.  test_conv_kernel_inventory lists every conv kernel family and mode the shipped library can name
-and asserts that the bound-checked case tables reach each one."""
+and asserts that the bound-checked case tables reach each one, the fp32 modes and row tiles (table of test_gpu_conv_f32_bounds.py) included."""
 import ctypes as C
 import re
 
@@ -329,6 +329,10 @@ INVENTORY = {
     'conv_wgrad_pp', 'conv_wgrad_f32', 'conv_wgrad_flat', 'conv_wgrad_stem', 'conv_wgrad_cols<1>', 'conv_wgrad_cols<2>',
     'conv_wgrad_rows<3>', 'conv_wgrad_rows<4>', 'conv_wgrad_ppg', 'conv_wgrad_flatg',
 }
+# the fp32 parity mode: every epilogue mode of conv_igemm<float> and every row tile of conv_wgrad_f32, reached by the table of
+# test_gpu_conv_f32_bounds.py (its names keep the element type; _key below drops it for the bf16 set above)
+INVENTORY_F32 = {'conv_igemm<float>/0', 'conv_igemm<float>/1', 'conv_igemm<float>/2', 'conv_igemm<float>/3', 'conv_igemm<float>/4',
+                 'conv_wgrad_f32<1>', 'conv_wgrad_f32<2>', 'conv_wgrad_f32<3>', 'conv_wgrad_f32<4>'}
 # compared against fp64 or bit for bit against bound-checked kernels by their own tests (not rewritten here)
 _STEM = 'test_gpu_stem_u8.py::test_stem_u8_kernels_vs_fp64_conv_of_the_three_affine_planes (conv_bounds.stem_u8_%s, per element)'
 COUNTED = {'stem_u8_fwd_kernel': _STEM % 'fwd', 'stem_u8_fwd_mfma_kernel': _STEM % 'fwd', 'stem_u8_wgrad_kernel': _STEM % 'wgrad',
@@ -346,6 +350,13 @@ def _key(name):
     if base in ('conv_wgrad_cols', 'conv_wgrad_rows'):
         return '%s<%s>' % (base, args[0])
     return base
+
+
+def _key_f32(name):
+    """'conv_igemm<float, 3, 2, 2, 4>' -> 'conv_igemm<float>/4'; 'conv_wgrad_f32<2>' stays"""
+    if name.startswith('conv_igemm<float,'):
+        return 'conv_igemm<float>/%s' % name[:-1].split(',')[-1].strip()
+    return name
 
 
 def _env(monkeypatch, env):
@@ -432,3 +443,10 @@ def test_conv_kernel_inventory(ctx, monkeypatch):
     assert not missing, 'conv kernels without a bound-checked case: %s' % sorted(missing)
     unknown = seen - INVENTORY - set(COUNTED)
     assert not unknown, 'kernels reached by the case tables but missing from INVENTORY: %s' % sorted(unknown)
+    import test_gpu_conv_f32_bounds as T2
+    _env(monkeypatch, T2.OFF)
+    seen32 = {_key_f32(n) for n in T2.f32_names(ctx)}
+    missing = INVENTORY_F32 - seen32
+    assert not missing, 'fp32 conv kernels without a bound-checked case: %s' % sorted(missing)
+    unknown = seen32 - INVENTORY_F32
+    assert not unknown, 'kernels reached by the fp32 table but missing from INVENTORY_F32: %s' % sorted(unknown)
