@@ -249,8 +249,9 @@ def test_fp32_mode_meets_the_north_star_tolerance(name, nc, B, S):
 @pytest.mark.parametrize('name,B,S', [('inception_v3', 6, 299), ('resnet18', 8, 224)])
 def test_train_steps_are_bitwise_reproducible(name, B, S):
     """Two replicas from the same seed, fed the same batches, stay bit-identical over several fused steps: every reduction
-    has a fixed order (no float atomics) and the program lanes are ordered by the static data flow -- a missing dependency
-    between lanes would show up here as diverging bits."""
+    has a fixed order (no float atomics) and the program lanes are ordered by the static data flow.  (At this batch the lanes hardly
+    overlap, so this run cannot be relied on to expose a missing dependency between lanes: tests/test_gpu_lane_order.py forces the
+    timing, tests/test_program_footprints_cpu.py audits the schedule against the pointers of the op tables.)"""
     from ifcb_classifier_amd import graph
     from ifcb_classifier_amd.engine import Engine
     engs = []
@@ -431,7 +432,9 @@ def test_roi_batch_whose_stem_output_passes_2_gib_equals_its_parts():
 def test_lane_count_does_not_change_the_result(monkeypatch):
     """The lane count only decides which stream a kernel is launched on (data-parallel jobs use 2 lanes, a single GPU 4, one
     lane is plain stream order): every reduction has a fixed order and the per-lane scratch buffers carry no state, so
-    1, 2 and 4 lanes must produce the same bits -- a dependency the 2- or 4-lane schedule misses would show up here."""
+    1, 2 and 4 lanes must produce the same bits.  (A dependency the 2- or 4-lane schedule misses changes the result only when the
+    timing goes wrong, which this batch rarely provokes: tests/test_gpu_lane_order.py slows each lane in turn on poisoned buffers to
+    force it, and tests/test_program_footprints_cpu.py audits the schedule against the pointers of the op tables.)"""
     from ifcb_classifier_amd import graph
     from ifcb_classifier_amd.engine import Engine
     B, S = 6, 299

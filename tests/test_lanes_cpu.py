@@ -5,28 +5,7 @@ far on the lanes of its wait mask."""
 import random
 
 from ifcb_classifier_amd.engine import schedule_lanes, _overlap
-
-
-def _happens_before(sched):
-    n = len(sched)
-    last_on_lane = {}
-    preds = [set() for _ in range(n)]
-    queued = {l: [] for l in range(8)}
-    for i, (lane, wait) in enumerate(sched):
-        if lane in last_on_lane:
-            preds[i].add(last_on_lane[lane])
-        for l in range(8):
-            if wait >> l & 1 and queued[l]:
-                preds[i].add(queued[l][-1])          # the tail of lane l (stream order covers everything before it)
-        last_on_lane[lane] = i
-        queued[lane].append(i)
-    # transitive closure (small n)
-    reach = [set() for _ in range(n)]
-    for i in range(n):
-        for p in preds[i]:
-            reach[i].add(p)
-            reach[i] |= reach[p]
-    return reach
+from program_footprints import happens_before as _happens_before
 
 
 def _random_program(rng, n, nl):
