@@ -200,3 +200,7 @@ __device__ __forceinline__ unsigned xcd_remap(unsigned bid, unsigned nblk) {
 }
 
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+
+// roi_turn.hip: the resize kernels for codes with a transpose bit (ifcbk_roi_preprocess with flip_bits_valid == 2)
+int ifcbk_roi_turn_launch(ifcbk_ctx* ctx, const ifcbk_roi_desc* d, const uint8_t* pixels, const int64_t* offs, const int32_t* hs,
+                          const int32_t* ws, const uint8_t* flips, int kmax, void* out, uint8_t* out_u8, hipStream_t st);

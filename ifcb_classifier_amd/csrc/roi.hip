@@ -329,6 +329,8 @@ extern "C" int ifcbk_roi_preprocess(ifcbk_ctx* ctx, const ifcbk_roi_desc* d, con
     if (need > ctx->ws_bytes) IFCBK_FAIL(ctx, IFCBK_ENOMEM, "roi_preprocess: workspace %zu > reserved %zu", need, ctx->ws_bytes);
     int kmax = kmax_for(max_h, max_w, d->S);
     hipStream_t st = (hipStream_t)stream;
+    if (d->flip_bits_valid == 2)                // codes with bit 2 = transpose (quarter turns): the kernels of roi_turn.hip, for the whole batch
+        return ifcbk_roi_turn_launch(ctx, d, pixels, offs, hs, ws, flips, kmax, out, out_u8, st);
     int nco = d->n_img * 2 * d->S;
     hipLaunchKernelGGL(roi_coeffs_kernel, dim3(cdiv(nco, 256)), dim3(256), 0, st, hs, ws, d->n_img, d->S, kmax, (int32_t*)ctx->ws);
     IFCBK_LAUNCH_CHECK(ctx, "roi_coeffs");

@@ -1693,21 +1693,22 @@ class Engine:
         self.in_kind[self.in_slot] = 'nhwc'
         return N
 
-    def load_rois(self, pixels, offs, hs, ws, max_h, max_w, in_channels=1, flips=None, mean=None, std=None, slot=None):
+    def load_rois(self, pixels, offs, hs, ws, max_h, max_w, in_channels=1, flips=None, mean=None, std=None, slot=None, turn=False):
         """ragged u8 ROIs (device tensors) -> input buffer via the PIL-exact resize kernel.  slot: the input slot of a
-        prefetch (runs on the prefetch stream with the prefetch context's workspace); None = the current slot, current stream."""
+        prefetch (runs on the prefetch stream with the prefetch context's workspace); None = the current slot, current stream.
+        turn: the codes in ``flips`` may hold bit 2 = transpose (TRAIN --rot90; neuston_data.fold_turns)."""
         if slot is not None:
             return self._load_rois_into(self.pre_ctx, C.c_void_p(self.pre_stream.cuda_stream), slot, False,
-                                        pixels, offs, hs, ws, max_h, max_w, in_channels, flips, mean, std)
+                                        pixels, offs, hs, ws, max_h, max_w, in_channels, flips, mean, std, turn)
         return self._load_rois_into(self.ctx, self.stream(), self.in_slot, True, pixels, offs, hs, ws, max_h,
-                                    max_w, in_channels, flips, mean, std)
+                                    max_w, in_channels, flips, mean, std, turn)
 
-    def _load_rois_into(self, ctx, stream, slot, main, pixels, offs, hs, ws, max_h, max_w, in_channels, flips, mean, std):
+    def _load_rois_into(self, ctx, stream, slot, main, pixels, offs, hs, ws, max_h, max_w, in_channels, flips, mean, std, turn=False):
         n = hs.numel()
         dst = self.in_bufs[slot]
         d = RoiDesc()
         d.n_img, d.S, d.in_channels, d.out_channels = n, self.net.S, in_channels, 8
-        d.flip_bits_valid = 1 if flips is not None else 0
+        d.flip_bits_valid = (2 if turn else 1) if flips is not None else 0
         d.dtype = self.cdtype
         for k in range(3):
             d.mean[k] = 0.0 if mean is None else float(mean[k])

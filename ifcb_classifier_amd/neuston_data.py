@@ -33,19 +33,34 @@ def default_loader(path):
 class RoiTransform:
     """What ``transforms.Compose([flips] + [Resize, ToTensor, Normalize?])`` means on the GPU path."""
 
-    def __init__(self, resize, img_norm=None, vflip=False, hflip=False):
+    def __init__(self, resize, img_norm=None, vflip=False, hflip=False, rot90=False):
         self.resize = resize
         self.img_norm = img_norm          # (mean[3], std[3]) or None
         self.vflip, self.hflip = vflip, hflip
+        self.rot90 = bool(rot90)          # --rot90: k counter-clockwise quarter turns after the flips, k uniform in {0, 1, 2, 3}
 
     def flip_code(self):
-        """bit0 = vertical flip ('x'), bit1 = horizontal flip ('y'); each with p = 0.5 (RandomVertical/HorizontalFlip)"""
+        """bit0 = vertical flip ('x'), bit1 = horizontal flip ('y'); each with p = 0.5 (RandomVertical/HorizontalFlip).
+        With rot90 the k quarter turns that follow the flips are folded in: bit2 = transpose (``fold_turns``).  The third random
+        number is drawn only with rot90 set, so the random stream of a run without it is unchanged."""
         code = 0
         if self.vflip and random.random() < 0.5:
             code |= 1
         if self.hflip and random.random() < 0.5:
             code |= 2
+        if self.rot90:
+            code = fold_turns(code & 1, code >> 1, random.randrange(4))
         return code
+
+
+def fold_turns(vflip, hflip, k):
+    """(vflip, hflip, then k counter-clockwise quarter turns) as the kernel's code byte: the image is
+    hflip^bit1( vflip^bit0( transpose^bit2( src ) ) ).  One turn is vflip(transpose(X)), and a transpose moved inside the flips
+    swaps them: (t, v, h) -> (t ^ 1, h ^ 1, v).  Each of the 16 inputs has exactly one such form."""
+    t, v, h = 0, int(bool(vflip)), int(bool(hflip))
+    for _ in range(k % 4):
+        t, v, h = t ^ 1, h ^ 1, v
+    return v | (h << 1) | (t << 2)
 
 
 class NeustonDataset(Dataset):
@@ -215,6 +230,8 @@ class NeustonDataset(Dataset):
         path = self.images[index]
         data = default_loader(path)
         flip = self.transforms.flip_code() if self.transforms is not None else 0
+        if self.transforms is not None and getattr(self.transforms, 'rot90', False):
+            return (data, flip, True), self.targets[index], path      # (third field: the transform turns, whatever this draw was)
         return (data, flip), self.targets[index], path
 
     def __len__(self):
@@ -271,8 +288,9 @@ def get_trainval_transforms(args):
     norm = parse_imgnorm(args.img_norm) if args.img_norm else None
     flip = args.flip or ''
     vflip, hflip = 'x' in flip, 'y' in flip                # 'x' = vertical, 'y' = horizontal (sic)
-    train = RoiTransform(args.resize, norm, vflip, hflip)
-    val = RoiTransform(args.resize, norm, vflip and '+V' in flip, hflip and '+V' in flip)
+    rot90 = getattr(args, 'rot90', None)                   # None (unset) | 'T' (training set) | '+V' (validation set as well)
+    train = RoiTransform(args.resize, norm, vflip, hflip, rot90=bool(rot90))
+    val = RoiTransform(args.resize, norm, vflip and '+V' in flip, hflip and '+V' in flip, rot90=rot90 == '+V')
     return train, val
 
 
@@ -326,10 +344,12 @@ class IfcbBinDataset(Dataset):
 
 # ------------------------------------------------------------------------------------------ batching
 def collate_rois(items):
-    """DataLoader collate_fn: [( (img_u8, flip), *rest )] -> (roi_batch dict, *rest lists).  One ragged u8 blob,
-    an int64 offset table and int32 dims; tensors are pinned by the loader (pin_memory=True)."""
+    """DataLoader collate_fn: [( (img_u8, flip[, turn]), *rest )] -> (roi_batch dict, *rest lists).  One ragged u8 blob,
+    an int64 offset table and int32 dims; tensors are pinned by the loader (pin_memory=True).  ``turn`` (items of a dataset whose
+    transform has rot90 set) marks the batch for the quarter-turn kernels whatever codes were drawn."""
     imgs = [it[0][0] for it in items]
     flips = [it[0][1] for it in items]
+    turn = any(len(it[0]) > 2 and it[0][2] for it in items)
     ch = 3 if any(im.ndim == 3 for im in imgs) else 1
     if ch == 3:
         imgs = [im if im.ndim == 3 else np.repeat(im[:, :, None], 3, 2) for im in imgs]
@@ -342,6 +362,8 @@ def collate_rois(items):
     blob = torch.from_numpy(np.concatenate([np.ascontiguousarray(im).reshape(-1) for im in imgs]))
     batch = dict(pixels=blob, offs=offs, hs=hs, ws=ws, flips=torch.tensor(flips, dtype=torch.uint8),
                  max_h=int(hs.max()), max_w=int(ws.max()), in_channels=ch)
+    if turn:
+        batch['turn'] = True
     rest = list(zip(*[it[1:] for it in items]))
     out = [batch]
     for r in rest:
@@ -355,7 +377,11 @@ def rois_to_device(batch, device, transform=None):
     kw = dict(pixels=batch['pixels'].to(device, non_blocking=True), offs=batch['offs'].to(device, non_blocking=True),
               hs=batch['hs'].to(device, non_blocking=True), ws=batch['ws'].to(device, non_blocking=True),
               max_h=batch['max_h'], max_w=batch['max_w'], in_channels=batch['in_channels'])
-    if batch['flips'].any():
+    if batch.get('turn') or (transform is not None and getattr(transform, 'rot90', False)):
+        # the codes may hold a transpose bit: always handed over, so the kernels a run launches do not depend on the draw
+        kw['flips'] = batch['flips'].to(device, non_blocking=True)
+        kw['turn'] = True
+    elif batch['flips'].any():
         kw['flips'] = batch['flips'].to(device, non_blocking=True)
     if transform is not None and transform.img_norm is not None:
         kw['mean'], kw['std'] = transform.img_norm

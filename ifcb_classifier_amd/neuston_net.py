@@ -551,6 +551,7 @@ def argparse_nn_train(train_subparser):
     epochs.add_argument('--estop', metavar='STOP', default=10, type=int, help='Early Stopping: Number of epochs following a best-epoch after-which to stop training. Set STOP=0 to disable. Default is 10')
     augs = t.add_argument_group(title='Augmentation Options')
     augs.add_argument('--flip', choices=['x', 'y', 'xy', 'x+V', 'y+V', 'xy+V'], help='Training images have 50%% chance of being flipped along the designated axis: (x) vertically, (y) horizontally, (xy) either/both. "+V" includes the Validation dataset')
+    augs.add_argument('--rot90', nargs='?', const='T', choices=['T', '+V'], default=None, help='(MI355X path, additive) Training images are rotated counter-clockwise by k quarter turns, k uniform in {0,1,2,3}, after any --flip and before the resize. "+V" includes the Validation dataset. With "--flip xy" the eight symmetries of the square are equally likely. Default (unset) is no rotation')
     out = t.add_argument_group(title='Output Options')
     out.add_argument('--outdir', default='training-output/{TRAIN_ID}', help='Default is "training-output/{TRAIN_ID}"')
     out.add_argument('--model-id', default='{TRAIN_ID}', help='Set a specific model id. Patterns {TRAIN_DATE} and {TRAIN_ID} are recognized. Default is "{TRAIN_ID}"')

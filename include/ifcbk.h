@@ -247,7 +247,11 @@ typedef struct {
     int32_t S;               /* output side (299 / 224)                                               */
     int32_t in_channels;     /* 1 (grayscale ROI -> 3 identical channels) or 3 (interleaved RGB)      */
     int32_t out_channels;    /* padded channel count of the NHWC output (8)                            */
-    int32_t flip_bits_valid; /* !=0: flips[i] bit0 = vertical flip ('x'), bit1 = horizontal ('y')     */
+    int32_t flip_bits_valid; /* !=0: flips[i] bit0 = vertical flip ('x'), bit1 = horizontal ('y');
+                                2: additionally bit2 = transpose (TRAIN --rot90).  The resize then sees
+                                hflip^bit1( vflip^bit0( transpose^bit2( src ) ) ), transpose(src)[r][c] = src[c][r];
+                                hs / ws / max_h / max_w stay the SOURCE dims.  With 0 or 1 bit 2 is ignored;
+                                with 2 a code below 4 gives the bytes that 1 gives                          */
     int32_t dtype;
     float   mean[3], std[3]; /* Normalize; std = 1, mean = 0 for none                                 */
     float   tin_scale[3], tin_shift[3]; /* [TV] transform_input affine (1,0 when off)                 */
