@@ -133,6 +133,11 @@ extern "C" const char* ifcbk_last_error(ifcbk_ctx* c) { return c ? c->err : g_cr
 static int run_one(ifcbk_ctx* c, const ifcbk_op* o, void* st) {
     void* const* p = o->p;
     const int acc = o->flags & 1, pacc = (o->flags >> 1) & 1;
+    // label smoothing (TRAIN --label-smoothing) rides on the two loss kinds: f[1] != 0 is the smoothing factor and goes to the smoothed
+    // kernel, with p[4] as the class weights of the _W kind and none for the plain kind; f[1] == 0 takes the cases below untouched
+    if ((o->kind == IFCBK_OP_SOFTMAX_XENT || o->kind == IFCBK_OP_SOFTMAX_XENT_W) && o->f[1] != 0.f)
+        return ifcbk_softmax_xent_ls(c, (const float*)p[0], (const int64_t*)p[1], o->kind == IFCBK_OP_SOFTMAX_XENT_W ? (const float*)p[4] : nullptr,
+                                     (int)o->i[0], (int)o->i[1], o->f[0], o->f[1], (float*)p[2], acc, (float*)p[3], st);
     switch (o->kind) {
         case IFCBK_OP_CONV_FWD: return ifcbk_conv2d_fwd(c, &o->u.conv, p[0], p[1], p[2], (float*)p[3], st);
         case IFCBK_OP_CONV_FWD_AFFINE:

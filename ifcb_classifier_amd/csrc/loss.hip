@@ -1,5 +1,6 @@
 // Class-weighted cross-entropy: nn.CrossEntropyLoss(weight=w), mean reduction (TRAIN --class-norm).  The unweighted loss keeps its
-// own kernel and entry point (pool_head.hip); this file is reached only when the engine holds class weights.
+// own kernel and entry point (pool_head.hip); this file is reached only when the engine holds class weights -- or a label-smoothing
+// factor (TRAIN --label-smoothing: softmax_xent_ls_kernel, with or without class weights).
 #include "common.h"
 #include <math.h>
 
@@ -69,6 +70,89 @@ __global__ __launch_bounds__(1024) void softmax_xent_w_kernel(const float* logit
     }
 }
 
+// Label-smoothed cross-entropy: nn.CrossEntropyLoss(weight=w, label_smoothing=eps), mean reduction (TRAIN --label-smoothing).  With C = NC,
+// p = softmax(l), w = class_weight (NULL: all ones), W = sum_n w[t_n], SW = sum_k w[k], c1 = 1 - eps, eC = eps / C:
+//   loss      = weight / W * sum_n [ c1 w[t_n] (-log p[n][t_n]) + eC sum_j w[j] (-log p[n][j]) ]
+//   d[n][j]   = weight / W * [ (c1 w[t_n] + eC SW) p[n][j] - c1 w[t_n] [j == t_n] - eC w[j] ]
+// The normaliser stays W (torch does not rescale it by eps).  softmax_xent_w_kernel's shape: one 1024-thread block, 4 lanes per sample,
+// fixed butterflies, fixed-order slot sums; W and SW come from one pre-pass (slot s takes the samples / classes s, s + 256, ... in
+// order; thread 0 sums the 256 partials of each in slot order and broadcasts) -- bitwise reproducible.  The smoothing term is summed as
+// the non-negative pieces w[j] * ((mx - l[j]) + log s): mx >= l[j], and s >= 1 because the row's maximum contributes expf(0) == 1 to a sum
+// of non-negative terms; sum w * lse - sum w * l would cancel.  Per sample: 2 NC expf and one logf as in the kernels above, and for the
+// smoothing NC (subtract, add, multiply-add) + 2 butterfly adds for the loss, NC (multiply, multiply-subtract) for dlogits.
+// eps == 0 computes softmax_xent_w's function through this kernel's own operations (not bit-equal to it).
+// A target outside [0, NC) is the caller's fault, as there; so is W == 0 (every target in a zero-weight class: torch gives NaN too).
+__global__ __launch_bounds__(1024) void softmax_xent_ls_kernel(const float* logits, const int64_t* target, const float* class_weight,
+                                                               int N, int NC, float weight, float eps, float* loss_out, int loss_acc,
+                                                               float* dlogits) {
+    __shared__ float sl[256];
+    __shared__ float sk[256];
+    __shared__ float sW[2];
+    const int sub = threadIdx.x & 3, slot = threadIdx.x >> 2;
+    if (sub == 0) {
+        float wsum = 0.f, ksum = 0.f;
+        for (int n = slot; n < N; n += 256) wsum += class_weight ? class_weight[(int)target[n]] : 1.f;
+        for (int k = slot; k < NC; k += 256) ksum += class_weight ? class_weight[k] : 1.f;
+        sl[slot] = wsum;
+        sk[slot] = ksum;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float s = 0.f, k = 0.f;
+        for (int i = 0; i < 256; ++i) s += sl[i];
+        for (int i = 0; i < 256; ++i) k += sk[i];
+        sW[0] = s;
+        sW[1] = k;
+    }
+    __syncthreads();
+    const float W = sW[0], SW = sW[1];
+    const float invW = 1.f / W;
+    const float g = weight / W;
+    const float c1 = 1.f - eps, eC = eps / (float)NC;
+    float local = 0.f;
+    for (int n0 = 0; n0 < N; n0 += 256) {
+        const int n = n0 + slot;
+        const bool ok = n < N;
+        const float* l = logits + (size_t)(ok ? n : 0) * NC;
+        float mx = -INFINITY;
+        for (int j = sub; j < NC; j += 4) mx = fmaxf(mx, l[j]);
+        mx = fmaxf(mx, __shfl_xor(mx, 1));
+        mx = fmaxf(mx, __shfl_xor(mx, 2));
+        float s = 0.f;
+        for (int j = sub; j < NC; j += 4) s += expf(l[j] - mx);
+        s += __shfl_xor(s, 1);
+        s += __shfl_xor(s, 2);
+        const float ls = logf(s);
+        float q = 0.f;
+        for (int j = sub; j < NC; j += 4) q += (class_weight ? class_weight[j] : 1.f) * ((mx - l[j]) + ls);
+        q += __shfl_xor(q, 1);
+        q += __shfl_xor(q, 2);
+        const int tg = ok ? (int)target[n] : 0;
+        const float wt = ok ? (class_weight ? class_weight[tg] : 1.f) : 0.f;
+        const float hard = c1 * wt;
+        if (ok && sub == 0) {
+            const float li = mx + ls - l[tg];
+            local += c1 * (wt * li) + eC * q;
+        }
+        if (ok && dlogits) {
+            float* d = dlogits + (size_t)n * NC;
+            const float is = 1.f / s;
+            const float A = hard + eC * SW;
+            for (int j = sub; j < NC; j += 4)
+                d[j] = g * (A * (expf(l[j] - mx) * is) - (j == tg ? hard : 0.f) - eC * (class_weight ? class_weight[j] : 1.f));
+        }
+    }
+    __syncthreads();                       // (thread 0 has finished reading the pre-pass partials)
+    if (sub == 0) sl[slot] = local;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float s = 0.f;
+        for (int i = 0; i < 256; ++i) s += sl[i];
+        s = s * invW * weight;
+        loss_out[0] = loss_acc ? loss_out[0] + s : s;
+    }
+}
+
 }  // namespace
 
 #define ST ((hipStream_t)stream)
@@ -81,5 +165,17 @@ extern "C" int ifcbk_softmax_xent_w(ifcbk_ctx* ctx, const float* logits, const i
     hipLaunchKernelGGL(softmax_xent_w_kernel, dim3(1), dim3(1024), 0, ST, logits, target, class_weight, N, NC, weight, loss_out,
                        loss_accumulate, dlogits);
     IFCBK_LAUNCH_CHECK(ctx, "softmax_xent_w");
+    return IFCBK_OK;
+}
+
+extern "C" int ifcbk_softmax_xent_ls(ifcbk_ctx* ctx, const float* logits, const int64_t* target, const float* class_weight, int N, int NC,
+                                     float weight, float label_smoothing, float* loss_out, int loss_accumulate, float* dlogits,
+                                     void* stream) {
+    if (N <= 0 || NC <= 0) IFCBK_FAIL(ctx, IFCBK_EINVAL, "softmax_xent_ls: empty");
+    if (!(label_smoothing >= 0.f && label_smoothing <= 1.f)) IFCBK_FAIL(ctx, IFCBK_EINVAL, "softmax_xent_ls: label_smoothing outside [0, 1]");
+    if (!logits || !target || !loss_out) IFCBK_FAIL(ctx, IFCBK_EINVAL, "softmax_xent_ls: NULL operand");
+    hipLaunchKernelGGL(softmax_xent_ls_kernel, dim3(1), dim3(1024), 0, ST, logits, target, class_weight, N, NC, weight, label_smoothing,
+                       loss_out, loss_accumulate, dlogits);
+    IFCBK_LAUNCH_CHECK(ctx, "softmax_xent_ls");
     return IFCBK_OK;
 }

@@ -180,7 +180,8 @@ class Engine:
         return max(1, _index_bytes() // per_img)
 
     def __init__(self, net, device=0, max_batch=32, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, dtype='bf16', optimizer='adam',
-                 momentum=0.0, plan_only=False, train_batch=None, dp_world=None, class_weights=None, weight_decay=0.0):
+                 momentum=0.0, plan_only=False, train_batch=None, dp_world=None, class_weights=None, weight_decay=0.0,
+                 label_smoothing=0.0):
         # dp_world: world size of the data-parallel job this replica belongs to (None: WORLD_SIZE of the launcher, else an
         # initialised torch.distributed group, else 1) -- it picks the program-lane default, and train_step_ddp checks it
         self._dp_world_arg = None if dp_world is None else int(dp_world)
@@ -204,6 +205,10 @@ class Engine:
             if not all(math.isfinite(w) and w >= 0 for w in class_weights) or not any(class_weights):
                 raise ValueError('class_weights must be finite, non-negative and not all zero')
         self._class_weights_arg = class_weights
+        # additive (TRAIN --label-smoothing): nn.CrossEntropyLoss(label_smoothing=eps) in the fused loss ops; None / 0.0: the hard loss
+        self.label_smoothing = float(label_smoothing or 0.0)
+        if not 0.0 <= self.label_smoothing <= 1.0:                # (a NaN fails both comparisons)
+            raise ValueError('label_smoothing must be in [0, 1]')
         self.net = net
         if dtype not in ('bf16', 'fp32'):
             raise ValueError("dtype must be 'bf16' (performance) or 'fp32' (parity mode)")
@@ -1406,14 +1411,17 @@ class Engine:
         # with class weights (TRAIN --class-norm): the same three ops as OP_SOFTMAX_XENT_W, the weight tensor as a fifth operand.
         # Loss ops carry no lane annotation: they are full barriers on lane 0, so the read-only weight tensor needs no resource entry
         xent, cw = (_lib.OP_SOFTMAX_XENT, ()) if self.class_weight is None else (_lib.OP_SOFTMAX_XENT_W, (_vp(self.class_weight),))
+        # label smoothing (TRAIN --label-smoothing) is the second scalar of the same ops, either kind: f[1] != 0 sends the op to the
+        # smoothed kernel (ifcbk_softmax_xent_ls); without it f[1] stays the zero of a fresh op and the tables are what they were
+        ls = (self.label_smoothing,) if self.label_smoothing > 0 else ()
         lossl.add(xent, 'loss', p=(_vp(main.logits), _vp(self.target), _vp(self.loss), _vp(main.dlogits)) + cw,
-                  i=(N, net.NC), f=(1.0,))
+                  i=(N, net.NC), f=(1.0,) + ls)
         for h in auxh:
             lossl.add(xent, 'loss_aux', p=(_vp(h.logits), _vp(self.target), _vp(self.loss), _vp(h.dlogits)) + cw,
-                      i=(N, net.NC), f=(0.4,), flags=1)
+                      i=(N, net.NC), f=(0.4,) + ls, flags=1)
         pl.loss = Program(lossl)
         evl = OpList()
-        evl.add(xent, 'val_loss', p=(_vp(main.logits), _vp(self.target), _vp(self.loss), None) + cw, i=(N, net.NC), f=(1.0,))
+        evl.add(xent, 'val_loss', p=(_vp(main.logits), _vp(self.target), _vp(self.loss), None) + cw, i=(N, net.NC), f=(1.0,) + ls)
         pl.eval_loss = Program(evl)
         sm = OpList()
         sm.add(_lib.OP_SOFTMAX, 'softmax', p=(_vp(main.logits), _vp(self.probs)), i=(N, net.NC))

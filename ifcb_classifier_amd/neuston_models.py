@@ -261,16 +261,19 @@ class NeustonModel(nn.Module):
         self.hparams = hparams
         mb = max_batch or getattr(hparams, 'batch_size', None) or 32
         opt = str(getattr(hparams, 'optimizer', None) or 'Adam').lower()
-        # additive (TRAIN --class-norm / --weight-decay): per-class loss weights and L2 weight decay; absent = upstream's behaviour
+        # additive (TRAIN --class-norm / --weight-decay / --label-smoothing): per-class loss weights, L2 weight decay and the smoothing
+        # factor of the loss; absent = upstream's behaviour
         cw = getattr(hparams, 'class_weights', None)
+        ls = float(getattr(hparams, 'label_smoothing', None) or 0.0)
         self.model = get_namebrand_model(hparams.MODEL, len(hparams.classes), hparams.pretrained, device, mb,
                                          getattr(hparams, 'precision', 'bf16') or 'bf16', optimizer=opt,
                                          lr=float(getattr(hparams, 'learning_rate', None) or 0.001),
                                          momentum=float(getattr(hparams, 'momentum', None) or 0.0), train_batch=train_batch,
-                                         class_weights=cw, weight_decay=float(getattr(hparams, 'weight_decay', None) or 0.0))
-        # what upstream would have written at neuston_models.py:55; the engine's fused loss ops compute the same weighted mean
+                                         class_weights=cw, weight_decay=float(getattr(hparams, 'weight_decay', None) or 0.0),
+                                         label_smoothing=ls)
+        # what upstream would have written at neuston_models.py:55; the engine's fused loss ops compute the same weighted, smoothed mean
         eng = self.model.engine
-        self.criterion = nn.CrossEntropyLoss() if cw is None else nn.CrossEntropyLoss(weight=eng.class_weight.clone())
+        self.criterion = nn.CrossEntropyLoss(weight=None if cw is None else eng.class_weight.clone(), label_smoothing=eng.label_smoothing)
         self.best_val_loss = np.inf
         self.best_epoch = 0
         self.agg_train_loss = 0.0

@@ -61,6 +61,13 @@ def _class_norm_power(text):
     return v
 
 
+def _label_smoothing(text):
+    v = float(text)
+    if not 0.0 <= v <= 1.0:                    # (nan fails both comparisons)
+        raise argparse.ArgumentTypeError('EPS must be in [0, 1], got %r' % text)
+    return v
+
+
 def _dist():
     import torch.distributed as dist
     if int(os.environ.get('WORLD_SIZE', 1)) > 1:
@@ -565,6 +572,7 @@ def argparse_nn_train(train_subparser):
     optim.add_argument('--momentum', default=0.0, type=float, help='SGD momentum. Default is 0')
     optim.add_argument('--weight-decay', default=0.0, type=float, help='L2 weight decay of every parameter, as torch.optim.Adam/SGD(weight_decay=WD) (not AdamW). Default is 0')
     optim.add_argument('--class-norm', metavar='POWER', nargs='?', const=1.0, type=_class_norm_power, default=None, help='Bias results to emphasize smaller classes: weight the loss of class c by n_c^-POWER (n_c: training images of the class), scaled to a mean weight of 1 per training image. POWER defaults to 1 ("balanced"); 0 weights all classes equally. Default (unset) is the unweighted loss')
+    optim.add_argument('--label-smoothing', metavar='EPS', default=0.0, type=_label_smoothing, help='Label smoothing of the loss, as nn.CrossEntropyLoss(label_smoothing=EPS): the target distribution is (1-EPS) one-hot + EPS/C uniform, for noisy annotations. A float in [0, 1]; val_loss follows the smoothed value. Default is 0 (hard labels)')
     meta = t.add_argument_group(title='Metadata and Annotations')
     meta.add_argument('--dataset-id', help='Associate a dataset id label with this model')
     meta.add_argument('--notes', help='Add any kind of note to the trained model.')

@@ -226,6 +226,15 @@ IFCBK_API int ifcbk_softmax(ifcbk_ctx*, const float* logits, int N, int NC, floa
  * unweighted loss keeps its own entry point).  All-ones weights give ifcbk_softmax_xent's results bit for bit.               */
 IFCBK_API int ifcbk_softmax_xent_w(ifcbk_ctx*, const float* logits, const int64_t* target, const float* class_weight, int N, int NC,
                          float weight, float* loss_out, int loss_accumulate, float* dlogits /*nullable*/, void* stream);
+/* the same with label smoothing (TRAIN --label-smoothing): nn.CrossEntropyLoss(weight=class_weight, label_smoothing=eps), mean
+ * reduction.  C = NC, p = softmax(logits), w = class_weight (NULL = all ones), W = sum_i w[target_i] (not rescaled by eps):
+ * loss_out[0] (+)= weight / W * sum_i [ (1 - eps) w[target_i] (-log p_i[target_i]) + eps / C * sum_j w[j] (-log p_i[j]) ];
+ * dlogits_i[j] = weight / W * [ ((1 - eps) w[target_i] + eps / C * sum_k w[k]) p_i[j] - (1 - eps) w[target_i] [j == target_i] - eps / C * w[j] ].
+ * IFCBK_EINVAL: label_smoothing outside [0, 1] or not finite, N or NC < 1, NULL logits / target / loss_out.  One block, fixed
+ * summation order: bitwise reproducible.  label_smoothing = 0 is the function of the two entry points above, not their bits.      */
+IFCBK_API int ifcbk_softmax_xent_ls(ifcbk_ctx*, const float* logits, const int64_t* target, const float* class_weight /*nullable*/, int N,
+                          int NC, float weight, float label_smoothing, float* loss_out, int loss_accumulate,
+                          float* dlogits /*nullable*/, void* stream);
 /* the bookkeeping of one fused train step, in the step's own op table (no framework kernel between the first and the last
  * launch of a step): num_batches_tracked[0..n) += 1 of every BatchNorm ([PL]/torch: nn.BatchNorm2d.forward in training) and
  * loss_sum += loss (the reference's train_loss is the SUM of the batch losses, neuston_models.py:85).  Either part may be NULL. */
@@ -385,7 +394,10 @@ enum {
     IFCBK_OP_STEP_COUNTERS,  /* p: num_batches_tracked (i64, nullable), loss_sum (nullable), loss; i[0] = number of BatchNorms      */
     IFCBK_OP_CONV_WGRAD_GROUP,/* p[0]: HOST array of i[0] ifcbk_wgrad_item entries, kept alive by the caller; p[1..]: the members' dw again
                                * (what the data-parallel bucket planner reads); flags bit 0 accumulate                            */
-    IFCBK_OP_SOFTMAX_XENT_W  /* p: logits, target, loss, dlogits (nullable), class_weight; i: N, NC; f[0] = weight; flags bit 0 accumulate */
+    IFCBK_OP_SOFTMAX_XENT_W  /* p: logits, target, loss, dlogits (nullable), class_weight; i: N, NC; f[0] = weight; flags bit 0 accumulate.
+                              * f[1] = label smoothing factor, for this kind and for IFCBK_OP_SOFTMAX_XENT (p: logits, target, loss, dlogits
+                              * (nullable); i: N, NC; f[0] = weight): 0, what a zeroed op holds, is the unsmoothed call; any other value
+                              * runs ifcbk_softmax_xent_ls with the same operands (class_weight = p[4] here, NULL for the plain kind)   */
 };
 typedef struct {
     ifcbk_conv_desc d;
