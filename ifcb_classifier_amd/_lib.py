@@ -90,6 +90,7 @@ _PROTOS = {
     'ifcbk_ctx_destroy': (_i, [_vp]),
     'ifcbk_ctx_reserve': (_i, [_vp, _sz]),
     'ifcbk_ctx_workspace_bytes': (_sz, [_vp]),
+    'ifcbk_ctx_workspace_ptr': (_vp, [_vp]),
     'ifcbk_ctx_set_lanes': (_i, [_vp, _i]),
     'ifcbk_ctx_live_graphs': (_i, [_vp]),
     'ifcbk_last_error': (C.c_char_p, [_vp]),
@@ -148,6 +149,8 @@ _PROTOS = {
     'ifcbk_sgd_flat': (_i, [_vp, _vp, _vp, _vp, C.c_int64, _f, _f, _f, _f, _vp]),
     'ifcbk_roi_preprocess': (_i, [_vp, C.POINTER(RoiDesc), _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     'ifcbk_roi_preprocess_workspace': (_sz, [C.POINTER(RoiDesc), _i, _i]),
+    'ifcbk_roi_preprocess_fit': (_i, [_vp, C.POINTER(RoiDesc), _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    'ifcbk_roi_preprocess_fit_workspace': (_sz, [C.POINTER(RoiDesc), _i, _i]),
     'ifcbk_u8_channel_moments': (_i, [_vp, _vp, _i, C.c_int64, _i, _vp, _vp]),
     'ifcbk_stem_u8_rows': (_i, [C.POINTER(ConvDesc)]),
     'ifcbk_stem_u8_fwd': (_i, [_vp, C.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
@@ -266,3 +269,12 @@ def ptr(t):
 def cur_stream():
     import torch
     return _vp(torch.cuda.current_stream().cuda_stream)
+
+
+def pad_fill(pad):
+    """the ``fill`` argument of ifcbk_roi_preprocess_fit for a ``pad`` setting: 'border' -> -1, a level 0..255 -> itself"""
+    if pad == 'border':
+        return -1
+    if isinstance(pad, bool) or not isinstance(pad, int) or not 0 <= pad <= 255:
+        raise ValueError("pad must be None, 'border' or an integer 0..255, got %r" % (pad,))
+    return int(pad)

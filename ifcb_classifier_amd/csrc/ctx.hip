@@ -116,6 +116,7 @@ extern "C" int ifcbk_ctx_reserve(ifcbk_ctx* c, size_t bytes) {
 }
 
 extern "C" size_t ifcbk_ctx_workspace_bytes(ifcbk_ctx* c) { return c ? c->ws_bytes : 0; }
+extern "C" void* ifcbk_ctx_workspace_ptr(ifcbk_ctx* c) { return c ? c->ws : nullptr; }
 
 extern "C" int ifcbk_ctx_set_lanes(ifcbk_ctx* c, int lanes) {
     if (!c || lanes < 1 || lanes > IFCBK_MAX_LANES) return IFCBK_EINVAL;

@@ -12,7 +12,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import Op, ConvDesc, BnDesc, PoolDesc, HeadDesc, RoiDesc
+from ._lib import Op, ConvDesc, BnDesc, PoolDesc, HeadDesc, RoiDesc, pad_fill
 
 
 # environment switches the library reads at launch time that change a workspace size or a partial-row count (csrc/conv_*.hip,
@@ -1701,17 +1701,19 @@ class Engine:
         self.in_kind[self.in_slot] = 'nhwc'
         return N
 
-    def load_rois(self, pixels, offs, hs, ws, max_h, max_w, in_channels=1, flips=None, mean=None, std=None, slot=None, turn=False):
+    def load_rois(self, pixels, offs, hs, ws, max_h, max_w, in_channels=1, flips=None, mean=None, std=None, slot=None, turn=False, pad=None):
         """ragged u8 ROIs (device tensors) -> input buffer via the PIL-exact resize kernel.  slot: the input slot of a
         prefetch (runs on the prefetch stream with the prefetch context's workspace); None = the current slot, current stream.
-        turn: the codes in ``flips`` may hold bit 2 = transpose (TRAIN --rot90; neuston_data.fold_turns)."""
+        turn: the codes in ``flips`` may hold bit 2 = transpose (TRAIN --rot90; neuston_data.fold_turns).
+        pad: None = squash to S x S (ifcbk_roi_preprocess); 'border' or a level 0..255 = keep the aspect ratio and fill the rest
+        (TRAIN --pad; ifcbk_roi_preprocess_fit)."""
         if slot is not None:
             return self._load_rois_into(self.pre_ctx, C.c_void_p(self.pre_stream.cuda_stream), slot, False,
-                                        pixels, offs, hs, ws, max_h, max_w, in_channels, flips, mean, std, turn)
+                                        pixels, offs, hs, ws, max_h, max_w, in_channels, flips, mean, std, turn, pad)
         return self._load_rois_into(self.ctx, self.stream(), self.in_slot, True, pixels, offs, hs, ws, max_h,
-                                    max_w, in_channels, flips, mean, std, turn)
+                                    max_w, in_channels, flips, mean, std, turn, pad)
 
-    def _load_rois_into(self, ctx, stream, slot, main, pixels, offs, hs, ws, max_h, max_w, in_channels, flips, mean, std, turn=False):
+    def _load_rois_into(self, ctx, stream, slot, main, pixels, offs, hs, ws, max_h, max_w, in_channels, flips, mean, std, turn=False, pad=None):
         n = hs.numel()
         dst = self.in_bufs[slot]
         d = RoiDesc()
@@ -1725,7 +1727,11 @@ class Engine:
         if self.net.transform_input:
             for k, (s, m) in enumerate(((0.229, 0.485), (0.224, 0.456), (0.225, 0.406))):
                 d.tin_scale[k], d.tin_shift[k] = s / 0.5, (m - 0.5) / 0.5
-        need = ctx.lib.ifcbk_roi_preprocess_workspace(C.byref(d), int(max_h), int(max_w))
+        if pad is None:
+            fn, fill = 'ifcbk_roi_preprocess', ()
+        else:
+            fn, fill = 'ifcbk_roi_preprocess_fit', (pad_fill(pad),)
+        need = getattr(ctx.lib, fn + '_workspace')(C.byref(d), int(max_h), int(max_w))
         if need > ctx.lib.ifcbk_ctx_workspace_bytes(ctx.h):
             if not main:
                 self.pre_stream.synchronize()        # an earlier prefetch may still read the arena that is about to move
@@ -1744,12 +1750,12 @@ class Engine:
                 with torch.cuda.stream(torch.cuda.current_stream(self.dev) if main else self.pre_stream):
                     self.in_ab[slot].copy_(torch.tensor(ab, dtype=torch.float32), non_blocking=False)
                 self._in_ab_host[slot] = ab
-            ctx.call('ifcbk_roi_preprocess', C.byref(d), _vp(pixels), _vp(offs), _vp(hs), _vp(ws), _vp(flips),
-                     int(max_h), int(max_w), None, _vp(self.in_u8[slot]), stream)
+            ctx.call(fn, C.byref(d), _vp(pixels), _vp(offs), _vp(hs), _vp(ws), _vp(flips),
+                     int(max_h), int(max_w), *fill, None, _vp(self.in_u8[slot]), stream)
             self.in_kind[slot] = 'u8'
             return n
-        ctx.call('ifcbk_roi_preprocess', C.byref(d), _vp(pixels), _vp(offs), _vp(hs), _vp(ws), _vp(flips),
-                 int(max_h), int(max_w), _vp(dst), None, stream)
+        ctx.call(fn, C.byref(d), _vp(pixels), _vp(offs), _vp(hs), _vp(ws), _vp(flips),
+                 int(max_h), int(max_w), *fill, _vp(dst), None, stream)
         self.in_kind[slot] = 'nhwc'
         return n
 

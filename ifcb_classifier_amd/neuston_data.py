@@ -33,8 +33,9 @@ def default_loader(path):
 class RoiTransform:
     """What ``transforms.Compose([flips] + [Resize, ToTensor, Normalize?])`` means on the GPU path."""
 
-    def __init__(self, resize, img_norm=None, vflip=False, hflip=False, rot90=False):
+    def __init__(self, resize, img_norm=None, vflip=False, hflip=False, rot90=False, pad=None):
         self.resize = resize
+        self.pad = parse_pad(pad)         # --pad: None = squash to resize x resize, 'border' / 0..255 = keep the aspect ratio, fill the rest
         self.img_norm = img_norm          # (mean[3], std[3]) or None
         self.vflip, self.hflip = vflip, hflip
         self.rot90 = bool(rot90)          # --rot90: k counter-clockwise quarter turns after the flips, k uniform in {0, 1, 2, 3}
@@ -51,6 +52,33 @@ class RoiTransform:
         if self.rot90:
             code = fold_turns(code & 1, code >> 1, random.randrange(4))
         return code
+
+
+def parse_pad(value):
+    """``--pad [FILL]`` / a checkpoint's ``pad``: None, 'border' or a grey level 0..255 (an int, or its decimal string)"""
+    if value is None or value == 'border':
+        return value
+    if isinstance(value, bool):
+        raise ValueError('pad: %r' % (value,))
+    if isinstance(value, (int, np.integer)):
+        v = int(value)
+    else:
+        text = str(value)
+        if not (text.isascii() and text.isdigit()):
+            raise ValueError("pad: FILL is 'border' or an integer 0..255, got %r" % (value,))
+        v = int(text)
+    if not 0 <= v <= 255:
+        raise ValueError("pad: FILL is 'border' or an integer 0..255, got %r" % (value,))
+    return v
+
+
+def pad_arg(text):
+    """argparse ``type=`` of ``--pad [FILL]`` (neuston_net TRAIN, neuston_util CALC_IMG_NORM)"""
+    import argparse
+    try:
+        return parse_pad(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError('FILL must be "border" or an integer 0..255, got %r' % text)
 
 
 def fold_turns(vflip, hflip, k):
@@ -289,18 +317,19 @@ def get_trainval_transforms(args):
     flip = args.flip or ''
     vflip, hflip = 'x' in flip, 'y' in flip                # 'x' = vertical, 'y' = horizontal (sic)
     rot90 = getattr(args, 'rot90', None)                   # None (unset) | 'T' (training set) | '+V' (validation set as well)
-    train = RoiTransform(args.resize, norm, vflip, hflip, rot90=bool(rot90))
-    val = RoiTransform(args.resize, norm, vflip and '+V' in flip, hflip and '+V' in flip, rot90=rot90 == '+V')
+    pad = getattr(args, 'pad', None)                       # geometry, not augmentation: both sets alike
+    train = RoiTransform(args.resize, norm, vflip, hflip, rot90=bool(rot90), pad=pad)
+    val = RoiTransform(args.resize, norm, vflip and '+V' in flip, hflip and '+V' in flip, rot90=rot90 == '+V', pad=pad)
     return train, val
 
 
 class ImageDataset(Dataset):
     """neuston_data.py:376-406 (RUN --type img).  No Normalize, as upstream (quirk: img_norm is ignored here)."""
 
-    def __init__(self, image_paths, resize=244, input_src=None):
+    def __init__(self, image_paths, resize=244, input_src=None, pad=None):
         self.input_src = input_src
         self.image_paths = [img for img in image_paths if img.endswith(IMG_EXTENSIONS)]
-        self.transform = RoiTransform(resize)
+        self.transform = RoiTransform(resize, pad=pad)
         if len(self.image_paths) < len(image_paths):
             print('{} non-image files were ommited'.format(len(image_paths) - len(self.image_paths)))
         if len(self.image_paths) == 0:
@@ -319,12 +348,12 @@ class IfcbBinDataset(Dataset):
     ``.images`` ({target_number: 2-D u8 array}); schema-v1 bins must already be stitched/infilled (pyifcb's
     ``InfilledImages`` is not available here: parity unpinned for that step)."""
 
-    def __init__(self, bin, resize, img_norm=None):
+    def __init__(self, bin, resize, img_norm=None, pad=None):
         self.bin = bin
         self.images, self.pids = [], []
         self.img_norm = parse_imgnorm(img_norm) if img_norm else None
         self.resize = resize[0] if isinstance(resize, (tuple, list)) else resize
-        self.transform = RoiTransform(self.resize, self.img_norm)
+        self.transform = RoiTransform(self.resize, self.img_norm, pad=pad)
         if getattr(bin, 'schema', None) == 'v1' and not getattr(bin, 'stitched', False) \
                 and os.environ.get('IFCBK_ALLOW_UNSTITCHED_V1', '0') == '0':
             # upstream reads old-style bins through pyifcb's InfilledImages (stitched ROI pairs, :446-449); that algorithm is
@@ -373,7 +402,7 @@ def collate_rois(items):
 
 
 def rois_to_device(batch, device, transform=None):
-    """upload a collated ROI batch (u8 blob + tables) and attach Normalize parameters."""
+    """upload a collated ROI batch (u8 blob + tables) and attach Normalize parameters and the transform's ``pad`` (when set)."""
     kw = dict(pixels=batch['pixels'].to(device, non_blocking=True), offs=batch['offs'].to(device, non_blocking=True),
               hs=batch['hs'].to(device, non_blocking=True), ws=batch['ws'].to(device, non_blocking=True),
               max_h=batch['max_h'], max_w=batch['max_w'], in_channels=batch['in_channels'])
@@ -385,4 +414,6 @@ def rois_to_device(batch, device, transform=None):
         kw['flips'] = batch['flips'].to(device, non_blocking=True)
     if transform is not None and transform.img_norm is not None:
         kw['mean'], kw['std'] = transform.img_norm
+    if transform is not None and getattr(transform, 'pad', None) is not None:
+        kw['pad'] = transform.pad
     return kw

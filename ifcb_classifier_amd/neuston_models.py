@@ -358,6 +358,8 @@ class NeustonModel(nn.Module):
                       max_h=res['max_h'], max_w=res['max_w'], in_channels=1)
             if transform is not None and transform.img_norm is not None:
                 kw['mean'], kw['std'] = transform.img_norm
+            if transform is not None and getattr(transform, 'pad', None) is not None:
+                kw['pad'] = transform.pad
             n = eng.load_rois(slot=slot, **kw)
         eng.prefetch_end(slot)
         return n

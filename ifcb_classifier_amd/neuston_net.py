@@ -21,7 +21,7 @@ from torch.utils.data import DataLoader
 
 from .neuston_callbacks import SaveValidationResults, SaveTestResults
 from .neuston_data import (get_trainval_datasets, IfcbBinDataset, ImageDataset, IMG_EXTENSIONS, collate_rois,
-                           rois_to_device)
+                           pad_arg, rois_to_device)
 from .neuston_models import NeustonModel, load_checkpoint_file, load_pretrained_weights
 
 
@@ -382,7 +382,7 @@ def do_training(args):
         # train at, where upstream's dummy input says 244
         from . import onnx_export
         output_path_onnx = os.path.join(args.outdir, args.model_id + '.onnx')
-        onnx_export.export(classifier.model.state_dict(), args.MODEL, args.classes, args.pretrained, output_path_onnx)
+        onnx_export.export(classifier.model.state_dict(), args.MODEL, args.classes, args.pretrained, output_path_onnx, pad=args.pad)
         print('EXPORTED:', output_path_onnx)
         onnx_export.write_classes(output_path_onnx + '.classes', args.classes)
         print('EXPORTED:', output_path_onnx + '.classes')
@@ -404,6 +404,7 @@ def do_run(args):
     if args.batch_size > classifier.model.engine.max_batch:
         args.batch_size = classifier.model.engine.max_batch          # per-image results: a smaller program batch changes nothing
     seed_everything(classifier.hparams.seed)
+    run_pad = getattr(classifier.hparams, 'pad', None)       # the geometry the model was trained on; absent in older files: squash
     # (a RUN batch beyond the 2 GiB buffer-descriptor window needs nothing here: results are per image, and the library cuts the
     #  convolutions of such a batch into launches over image groups)
     if os.path.isdir(args.SRC) and not args.SRC.endswith(os.sep):
@@ -464,7 +465,7 @@ def do_run(args):
                     continue
             n_bins += 1
             try:
-                ds = IfcbBinDataset(bin_fileset, classifier.hparams.resize, classifier.hparams.img_norm)
+                ds = IfcbBinDataset(bin_fileset, classifier.hparams.resize, classifier.hparams.img_norm, pad=run_pad)
                 if len(ds) == 0:
                     error_bins.append((bin_obj, AssertionError('Bin is Empty')))
                     continue
@@ -515,7 +516,7 @@ def do_run(args):
                 elif filter_mode == 'OUT' and any(k in img for k in filter_keywords):
                     img_paths.remove(img)
         assert len(img_paths) > 0, 'No images to process'
-        ds = ImageDataset(img_paths, resize=classifier.hparams.resize, input_src=args.SRC)
+        ds = ImageDataset(img_paths, resize=classifier.hparams.resize, input_src=args.SRC, pad=run_pad)
         loader = DataLoader(ds, batch_size=args.batch_size, pin_memory=True, num_workers=args.loaders,
                             collate_fn=collate_rois)
         trainer.test(classifier, loader, args.SRC, ds.transform, callbacks)
@@ -544,6 +545,7 @@ def argparse_nn_train(train_subparser):
     model = t.add_argument_group(title='Model Adjustments', description=None)
     model.add_argument('--untrain', dest='pretrained', default=True, action='store_false', help='If set, initializes MODEL ~without~ pretrained neurons. Default (unset) is pretrained')
     model.add_argument('--weights', metavar='PATH', default=os.environ.get('IFCBK_PRETRAINED_WEIGHTS'), help='(MI355X path, additive) torchvision state_dict (.pth) standing in for the ImageNet weights the reference downloads when --untrain is not set; there is no network / torchvision here. Default: $IFCBK_PRETRAINED_WEIGHTS')
+    model.add_argument('--pad', metavar='FILL', nargs='?', const='border', type=pad_arg, default=None, help='(MI355X path, additive) Keep each image\'s aspect ratio: resize it to fit the square input (PIL.ImageOps.pad, bilinear, centred) and fill the rest with FILL, instead of stretching it. FILL is "border" (per image, the mean level of its border pixels; the bare flag) or a grey level 0..255. Applies to the training and the validation set; RUN reads it from the model file. Put the bare flag behind the positionals (before them argparse takes SRC for FILL). Default (unset) stretches to the square')
     model.add_argument('--img-norm', nargs=2, metavar=('MEAN', 'STD'), help='Normalize images by MEAN and STD. eg1: "0.667 0.161", eg2: "0.056,0.058,0.051 0.067,0.071,0.057"')
     data = t.add_argument_group(title='Dataset Adjustments', description=None)
     data.add_argument('--seed', default=0, type=int, help='Set a specific seed for deterministic output & dataset-splitting reproducability.')

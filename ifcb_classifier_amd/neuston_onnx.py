@@ -35,7 +35,7 @@ def do_export(args):
     print(hp['MODEL'])
     # (--device is accepted for upstream's command line: the file is written from the checkpoint's tensors on the host)
     onnx_export.export(ckpt['state_dict'], hp['MODEL'], classes, hp.get('pretrained', False), output, half=args.half,
-                       opset=args.opset, batch_size=args.batchsize)
+                       opset=args.opset, batch_size=args.batchsize, pad=hp.get('pad'))
     print('EXPORTED:', output)
     output_classes = output.replace('.onnx', '.classes')
     onnx_export.write_classes(output_classes, classes)
@@ -109,7 +109,7 @@ def do_run(args):
     model = onnx_export.read(args.MODEL)
     if 'ifcbk.model' in model['metadata']:
         classifier, resize = load_backbone(model, args.precision, device=int(os.environ.get('LOCAL_RANK', 0)))
-        image_dataset = ImageDataset(img_paths, resize=resize, input_src=args.SRC)
+        image_dataset = ImageDataset(img_paths, resize=resize, input_src=args.SRC, pad=onnx_export.read_pad(model['metadata']))
         logits, out = classify(classifier, image_dataset)
     else:
         try:

@@ -16,6 +16,8 @@ from fractions import Fraction
 
 import numpy as np
 
+from .neuston_data import pad_arg
+
 
 # ------------------------------------------------------------------------------------------ CALC_IMG_NORM
 def _round_f32(cmp, guess):
@@ -85,9 +87,10 @@ def reduce_batches(moments, num_batches):
     return mean, std0
 
 
-def gpu_moments(loader, resize, device=0):
+def gpu_moments(loader, resize, device=0, pad=None):
     """per batch of ``loader`` (``collate_rois`` batches): resize on the GPU to the u8 plane, then its channel moments; yields
-    (sum_v, sum_v2, count) as Python integers, one entry per channel of the plane (1 for grey batches, 3 otherwise)"""
+    (sum_v, sum_v2, count) as Python integers, one entry per channel of the plane (1 for grey batches, 3 otherwise).
+    pad: as ``Engine.load_rois`` (the statistics of a padded dataset include the padding)"""
     import ctypes as C
     import torch
     from . import _lib
@@ -107,14 +110,15 @@ def gpu_moments(loader, resize, device=0):
             kw = rois_to_device(batch[0], dev)
             n, ch = int(kw['hs'].numel()), int(kw['in_channels'])
             d.n_img, d.in_channels = n, ch
-            need = ctx.lib.ifcbk_roi_preprocess_workspace(C.byref(d), kw['max_h'], kw['max_w'])
+            fn, fill = ('ifcbk_roi_preprocess', ()) if pad is None else ('ifcbk_roi_preprocess_fit', (_lib.pad_fill(pad),))
+            need = getattr(ctx.lib, fn + '_workspace')(C.byref(d), kw['max_h'], kw['max_w'])
             if need > ctx.lib.ifcbk_ctx_workspace_bytes(ctx.h):
                 ctx.reserve(need)
             plane = torch.empty((n, resize, resize, ch), dtype=torch.uint8, device=dev)
             mom = torch.empty((n, ch, 2), dtype=torch.int64, device=dev)        # uint64 bits; every sum is < 2^63
             stream = _lib.cur_stream()
-            ctx.call('ifcbk_roi_preprocess', C.byref(d), _lib.ptr(kw['pixels']), _lib.ptr(kw['offs']), _lib.ptr(kw['hs']),
-                     _lib.ptr(kw['ws']), None, kw['max_h'], kw['max_w'], None, _lib.ptr(plane), stream)
+            ctx.call(fn, C.byref(d), _lib.ptr(kw['pixels']), _lib.ptr(kw['offs']), _lib.ptr(kw['hs']),
+                     _lib.ptr(kw['ws']), None, kw['max_h'], kw['max_w'], *fill, None, _lib.ptr(plane), stream)
             ctx.call('ifcbk_u8_channel_moments', _lib.ptr(plane), n, resize * resize, ch, _lib.ptr(mom), stream)
             m = mom.cpu().numpy().view(np.uint64).astype(object).sum(axis=0)      # [ch][2], Python integers
             yield [int(v) for v in m[:, 0]], [int(v) for v in m[:, 1]], n * resize * resize
@@ -135,7 +139,10 @@ def calc_img_norm(args):
     loaders = getattr(args, 'loaders', 4)
     dataloader = DataLoader(nd, batch_size=args.batch_size, shuffle=False, num_workers=loaders, collate_fn=collate_rois,
                             pin_memory=True)
-    return reduce_batches(gpu_moments(dataloader, args.resize), len(dataloader))
+    pad = getattr(args, 'pad', None)
+    # (without --pad the call is the two-argument one it always was: callers that swap gpu_moments for a host twin keep working)
+    moments = gpu_moments(dataloader, args.resize) if pad is None else gpu_moments(dataloader, args.resize, pad=pad)
+    return reduce_batches(moments, len(dataloader))
 
 
 # ------------------------------------------------------------------------------------------ config makers
@@ -239,6 +246,7 @@ def argparse_init():
     imgnorm.add_argument('--class-min', metavar='MIN', default=2, type=int, help='Exclude classes with fewer than MIN instances. Default is 2')
     imgnorm.add_argument('--class-max', metavar='MAX', default=None, type=int, help='Limit classes to a MAX number of instances. '
                          'If multiple datasets are specified with a dataset-configuration csv, classes from lower-priority datasets are truncated first.')
+    imgnorm.add_argument('--pad', metavar='FILL', nargs='?', const='border', type=pad_arg, default=None, help='(MI355X path, additive) Statistics of the dataset as "neuston_net TRAIN --pad [FILL]" sees it: aspect ratio kept, the rest of the square filled with FILL ("border", the bare flag, or a grey level 0..255); the padding counts. Put the bare flag behind SRC')
     imgnorm.add_argument('--batch-size', metavar='B', default=108, type=int, help='Number of images per minibatch')
     imgnorm.add_argument('--loaders', metavar='N', default=4, type=int, help='Number of data-loading worker processes. Default is 4')
     return parser

@@ -212,9 +212,10 @@ def _emit(net, em, x_in):
         raise ValueError('%s: the graph has no classifier head' % net.name)
 
 
-def export(state_dict, model_name, classes, pretrained, path, half=False, opset=12, batch_size=0):
+def export(state_dict, model_name, classes, pretrained, path, half=False, opset=12, batch_size=0, pad=None):
     """Write the eval-mode ``model_name`` with the tensors of ``state_dict`` (torchvision keys; a checkpoint's ``model.``
-    prefix is dropped) to ``path``.  ``batch_size=0``: dynamic batch dim ``batch_size``.  Returns the number of bytes written."""
+    prefix is dropped) to ``path``.  ``batch_size=0``: dynamic batch dim ``batch_size``.  ``pad`` (the model's TRAIN --pad setting) is recorded as ``ifcbk.pad`` when
+    set; ``read_pad`` decodes it.  Returns the number of bytes written."""
     if opset not in OPSETS:
         raise ValueError('opset %d: this writer emits opsets %d..%d' % (opset, OPSETS[0], OPSETS[-1]))
     sd = {(k[len('model.'):] if k.startswith('model.') else k): v for k, v in state_dict.items()}
@@ -240,6 +241,9 @@ def export(state_dict, model_name, classes, pretrained, path, half=False, opset=
          + _bytes(11, _value_info('input', elem, [b, 3, net.S, net.S])) + _bytes(12, _value_info('output', elem, [b, net.NC])))
     meta = dict(model=model_name, num_classes=str(net.NC), pretrained=str(int(bool(pretrained))), resize=str(net.S),
                 version=FORMAT_VERSION)
+    if pad is not None:
+        from .neuston_data import parse_pad
+        meta['pad'] = str(parse_pad(pad))
     from . import __version__
     m = (_int(1, _ir_version(opset)) + _bytes(2, 'ifcb_classifier_amd') + _bytes(3, __version__) + _bytes(7, g)
          + _bytes(8, _bytes(1, '') + _int(2, opset))
@@ -249,6 +253,12 @@ def export(state_dict, model_name, classes, pretrained, path, half=False, opset=
     with open(path, 'wb') as f:
         f.write(m)
     return len(m)
+
+
+def read_pad(metadata):
+    """the ``pad`` setting of a file's ``metadata`` dict (``read(path)['metadata']``): None without ``ifcbk.pad``"""
+    from .neuston_data import parse_pad
+    return parse_pad(metadata.get('ifcbk.pad'))
 
 
 def write_classes(path, classes):

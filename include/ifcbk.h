@@ -47,6 +47,8 @@ IFCBK_API int  ifcbk_ctx_destroy(ifcbk_ctx* ctx);
 /* grow the ctx-owned workspace (split-K slabs, resize coefficient tables) to >= bytes; syncs the device */
 IFCBK_API int  ifcbk_ctx_reserve(ifcbk_ctx* ctx, size_t bytes);
 IFCBK_API size_t ifcbk_ctx_workspace_bytes(ifcbk_ctx* ctx);
+/* device address of the arena the entry points called outside a program use (tests: guard bytes behind what a call may write) */
+IFCBK_API void* ifcbk_ctx_workspace_ptr(ifcbk_ctx* ctx);
 /* number of program lanes (see ifcbk_op.flags; 1..8, default 4) that get a workspace arena from ifcbk_ctx_reserve; call before the
  * first reserve.  A program that names a lane beyond it is refused. */
 IFCBK_API int  ifcbk_ctx_set_lanes(ifcbk_ctx* ctx, int lanes);
@@ -271,6 +273,17 @@ IFCBK_API int ifcbk_roi_preprocess(ifcbk_ctx*, const ifcbk_roi_desc*, const uint
                          const int32_t* hs, const int32_t* ws, const uint8_t* flips, int max_h, int max_w,
                          void* out, uint8_t* out_u8 /*nullable: resized u8 [n,S,S,in_channels]*/, void* stream);
 IFCBK_API size_t ifcbk_roi_preprocess_workspace(const ifcbk_roi_desc*, int max_h, int max_w);
+/* Aspect-preserving twin (TRAIN --pad): the image the resize sees (after the flip / transpose code, as above) is resized to the
+ * inner size of PIL.ImageOps.contain -- the long side to S, the short side to round(short / long * S), half to even, at least 1 --
+ * with the same Pillow-exact arithmetic, and pasted at rint((S - n) / 2) into an S x S plane of FILL:
+ * PIL.ImageOps.pad(img, (S, S), BILINEAR, color = FILL, centering = (0.5, 0.5)).  fill: a level 0..255 for every channel, or
+ * -1 = per ROI and channel the rounded mean of the source ROI's border pixels.  Fill pixels pass through the float stage like any
+ * other.  flip_bits_valid 0 / 1 / 2 as above; out / out_u8 as above (either may be NULL, not both).  A ROI larger than
+ * max_h x max_w is cut to that size.  The workspace differs from ifcbk_roi_preprocess_workspace (the short axis needs more taps). */
+IFCBK_API int ifcbk_roi_preprocess_fit(ifcbk_ctx*, const ifcbk_roi_desc*, const uint8_t* pixels, const int64_t* offs,
+                         const int32_t* hs, const int32_t* ws, const uint8_t* codes, int max_h, int max_w,
+                         int fill /* 0..255, or -1 = border */, void* out, uint8_t* out_u8, void* stream);
+IFCBK_API size_t ifcbk_roi_preprocess_fit_workspace(const ifcbk_roi_desc*, int max_h, int max_w);
 /* per-image, per-channel integer moments of a u8 plane [n_img][pixels_per_img][channels] (channels 1..4):
    out[i][c][0] = sum of v, out[i][c][1] = sum of v*v, exact (uint64); n_img = 0 is a no-op.
  * x is typically out_u8 of ifcbk_roi_preprocess; mean = sum v / (255 n), population std from the two sums.
