@@ -136,9 +136,15 @@ static int run_one(ifcbk_ctx* c, const ifcbk_op* o, void* st) {
     const int acc = o->flags & 1, pacc = (o->flags >> 1) & 1;
     // label smoothing (TRAIN --label-smoothing) rides on the two loss kinds: f[1] != 0 is the smoothing factor and goes to the smoothed
     // kernel, with p[4] as the class weights of the _W kind and none for the plain kind; f[1] == 0 takes the cases below untouched
+    if ((o->kind == IFCBK_OP_SOFTMAX_XENT || o->kind == IFCBK_OP_SOFTMAX_XENT_W) && o->f[1] != 0.f && o->f[2] != 0.f)
+        IFCBK_FAIL(c, IFCBK_EINVAL, "softmax_xent op: label smoothing (f[1]) and focal gamma (f[2]) are both set");
     if ((o->kind == IFCBK_OP_SOFTMAX_XENT || o->kind == IFCBK_OP_SOFTMAX_XENT_W) && o->f[1] != 0.f)
         return ifcbk_softmax_xent_ls(c, (const float*)p[0], (const int64_t*)p[1], o->kind == IFCBK_OP_SOFTMAX_XENT_W ? (const float*)p[4] : nullptr,
                                      (int)o->i[0], (int)o->i[1], o->f[0], o->f[1], (float*)p[2], acc, (float*)p[3], st);
+    // focal loss (TRAIN --focal-gamma) rides on them the same way: f[2] != 0 is gamma and goes to the focal kernel; the two do not combine
+    if ((o->kind == IFCBK_OP_SOFTMAX_XENT || o->kind == IFCBK_OP_SOFTMAX_XENT_W) && o->f[2] != 0.f)
+        return ifcbk_softmax_xent_focal(c, (const float*)p[0], (const int64_t*)p[1], o->kind == IFCBK_OP_SOFTMAX_XENT_W ? (const float*)p[4] : nullptr,
+                                        (int)o->i[0], (int)o->i[1], o->f[0], o->f[2], (float*)p[2], acc, (float*)p[3], st);
     switch (o->kind) {
         case IFCBK_OP_CONV_FWD: return ifcbk_conv2d_fwd(c, &o->u.conv, p[0], p[1], p[2], (float*)p[3], st);
         case IFCBK_OP_CONV_FWD_AFFINE:

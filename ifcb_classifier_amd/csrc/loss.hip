@@ -1,7 +1,9 @@
 // Class-weighted cross-entropy: nn.CrossEntropyLoss(weight=w), mean reduction (TRAIN --class-norm).  The unweighted loss keeps its
 // own kernel and entry point (pool_head.hip); this file is reached only when the engine holds class weights -- or a label-smoothing
-// factor (TRAIN --label-smoothing: softmax_xent_ls_kernel, with or without class weights).
+// factor (TRAIN --label-smoothing: softmax_xent_ls_kernel, with or without class weights), or a focusing exponent (TRAIN --focal-gamma:
+// softmax_xent_focal_kernel, with or without class weights).
 #include "common.h"
+#include <float.h>
 #include <math.h>
 
 namespace {
@@ -153,6 +155,90 @@ __global__ __launch_bounds__(1024) void softmax_xent_ls_kernel(const float* logi
     }
 }
 
+// Focal loss (TRAIN --focal-gamma): with p = softmax(l), w = class_weight (NULL: all ones), W = sum_n w[t_n], g = gamma >= 0,
+//   u_n = 1 - p[n][t_n],  L_n = -log p[n][t_n]
+//   loss    = weight / W * sum_n w[t_n] u_n^g L_n
+//   d[n][j] = weight / W * w[t_n] (p[n][j] - [j == t_n]) (u_n^g + g p[n][t_n] u_n^(g-1) L_n)
+// The normaliser stays W, so g -> 0 is softmax_xent_w's function and the class weights are focal loss's per-class alpha.
+// softmax_xent_ls_kernel's shape: one 1024-thread block, 4 lanes per sample, fixed butterflies, fixed-order slot sums, one pre-pass for W
+// -- bitwise reproducible.  Three points of the arithmetic:
+//   u is so / s with so = sum_{j != t} expf(l_j - mx), the sum s with the target's term left out: non-negative terms, no cancellation
+//     (1 - p_t and s - e_t cancel when the target is the row's maximum: e_t == 1).  Term by term so's chain is below s's, so u <= 1.
+//     The target's dlogits element is -u, not p_t - 1, for the same reason.
+//   u^g is expf(g * logf(u)) for u > 0; for u == 0 it is 0 (g > 0) or 1 (g == 0).
+//   the bracket is pw + (g p_t) (pw (L / u)) with L / u taken as 0 when u == 0: both terms non-negative and finite for every g > 0, g < 1
+//     included (u^(g-1) alone is infinite at 0).  L = (mx + log s) - l_t >= 0: s >= 1, and rounding is monotone.  When u is below 2^-25
+//     the target is the maximum, s rounds to 1 and L is exactly 0, so L / u cannot overflow.
+// A row whose other classes' exponentials all flush to zero (u == 0; NC == 1 always) gives a loss term of 0 and a zero dlogits row for
+// g > 0.  Per sample: NC expf, one logf for L, logf + expf for the power, two divisions (u, L / u) and 1 / s; for dlogits NC more expf and
+// NC products.  g == 0 computes softmax_xent_w's function through this kernel's own operations (not bit-equal to it).
+// A target outside [0, NC) is the caller's fault, as there; so is W == 0 (NaN).
+__global__ __launch_bounds__(1024) void softmax_xent_focal_kernel(const float* logits, const int64_t* target, const float* class_weight,
+                                                                  int N, int NC, float weight, float gam, float* loss_out, int loss_acc,
+                                                                  float* dlogits) {
+    __shared__ float sl[256];
+    __shared__ float sW;
+    const int sub = threadIdx.x & 3, slot = threadIdx.x >> 2;
+    if (sub == 0) {
+        float wsum = 0.f;
+        for (int n = slot; n < N; n += 256) wsum += class_weight ? class_weight[(int)target[n]] : 1.f;
+        sl[slot] = wsum;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float s = 0.f;
+        for (int i = 0; i < 256; ++i) s += sl[i];
+        sW = s;
+    }
+    __syncthreads();
+    const float W = sW;
+    const float invW = 1.f / W;
+    float local = 0.f;
+    for (int n0 = 0; n0 < N; n0 += 256) {
+        const int n = n0 + slot;
+        const bool ok = n < N;
+        const float* l = logits + (size_t)(ok ? n : 0) * NC;
+        const int tg = ok ? (int)target[n] : 0;
+        float mx = -INFINITY;
+        for (int j = sub; j < NC; j += 4) mx = fmaxf(mx, l[j]);
+        mx = fmaxf(mx, __shfl_xor(mx, 1));
+        mx = fmaxf(mx, __shfl_xor(mx, 2));
+        float s = 0.f, so = 0.f;
+        for (int j = sub; j < NC; j += 4) {
+            const float e = expf(l[j] - mx);
+            s += e;
+            so += j == tg ? 0.f : e;
+        }
+        s += __shfl_xor(s, 1);
+        s += __shfl_xor(s, 2);
+        so += __shfl_xor(so, 1);
+        so += __shfl_xor(so, 2);
+        const float wt = ok ? (class_weight ? class_weight[tg] : 1.f) : 0.f;
+        const float li = mx + logf(s) - l[tg];
+        const float u = so / s;
+        const float pw = u > 0.f ? expf(gam * logf(u)) : (gam == 0.f ? 1.f : 0.f);
+        if (ok && sub == 0) local += wt * (pw * li);
+        if (ok && dlogits) {
+            float* d = dlogits + (size_t)n * NC;
+            const float is = 1.f / s;
+            const float pt = expf(l[tg] - mx) * is;
+            const float r = u > 0.f ? li / u : 0.f;
+            const float br = pw + (gam * pt) * (pw * r);
+            const float cb = weight * (wt / W) * br;
+            for (int j = sub; j < NC; j += 4) d[j] = cb * (j == tg ? -u : expf(l[j] - mx) * is);
+        }
+    }
+    __syncthreads();                       // (thread 0 has finished reading the W partials)
+    if (sub == 0) sl[slot] = local;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float s = 0.f;
+        for (int i = 0; i < 256; ++i) s += sl[i];
+        s = s * invW * weight;
+        loss_out[0] = loss_acc ? loss_out[0] + s : s;
+    }
+}
+
 }  // namespace
 
 #define ST ((hipStream_t)stream)
@@ -177,5 +263,16 @@ extern "C" int ifcbk_softmax_xent_ls(ifcbk_ctx* ctx, const float* logits, const 
     hipLaunchKernelGGL(softmax_xent_ls_kernel, dim3(1), dim3(1024), 0, ST, logits, target, class_weight, N, NC, weight, label_smoothing,
                        loss_out, loss_accumulate, dlogits);
     IFCBK_LAUNCH_CHECK(ctx, "softmax_xent_ls");
+    return IFCBK_OK;
+}
+
+extern "C" int ifcbk_softmax_xent_focal(ifcbk_ctx* ctx, const float* logits, const int64_t* target, const float* class_weight, int N, int NC,
+                                        float weight, float gamma, float* loss_out, int loss_accumulate, float* dlogits, void* stream) {
+    if (N <= 0 || NC <= 0) IFCBK_FAIL(ctx, IFCBK_EINVAL, "softmax_xent_focal: empty");
+    if (!(gamma >= 0.f && gamma <= FLT_MAX)) IFCBK_FAIL(ctx, IFCBK_EINVAL, "softmax_xent_focal: gamma negative or not finite");
+    if (!logits || !target || !loss_out) IFCBK_FAIL(ctx, IFCBK_EINVAL, "softmax_xent_focal: NULL operand");
+    hipLaunchKernelGGL(softmax_xent_focal_kernel, dim3(1), dim3(1024), 0, ST, logits, target, class_weight, N, NC, weight, gamma, loss_out,
+                       loss_accumulate, dlogits);
+    IFCBK_LAUNCH_CHECK(ctx, "softmax_xent_focal");
     return IFCBK_OK;
 }

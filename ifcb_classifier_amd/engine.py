@@ -181,7 +181,7 @@ class Engine:
 
     def __init__(self, net, device=0, max_batch=32, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, dtype='bf16', optimizer='adam',
                  momentum=0.0, plan_only=False, train_batch=None, dp_world=None, class_weights=None, weight_decay=0.0,
-                 label_smoothing=0.0):
+                 label_smoothing=0.0, focal_gamma=0.0):
         # dp_world: world size of the data-parallel job this replica belongs to (None: WORLD_SIZE of the launcher, else an
         # initialised torch.distributed group, else 1) -- it picks the program-lane default, and train_step_ddp checks it
         self._dp_world_arg = None if dp_world is None else int(dp_world)
@@ -209,6 +209,12 @@ class Engine:
         self.label_smoothing = float(label_smoothing or 0.0)
         if not 0.0 <= self.label_smoothing <= 1.0:                # (a NaN fails both comparisons)
             raise ValueError('label_smoothing must be in [0, 1]')
+        # additive (TRAIN --focal-gamma): focal loss u^gamma * CE in the fused loss ops, u = 1 - p[target]; None / 0.0: the plain loss
+        self.focal_gamma = float(focal_gamma or 0.0)
+        if not 0.0 <= self.focal_gamma < math.inf:                # (a NaN fails both comparisons)
+            raise ValueError('focal_gamma must be finite and not negative')
+        if self.focal_gamma > 0 and self.label_smoothing > 0:
+            raise ValueError('focal_gamma and label_smoothing do not combine: give one of them')
         self.net = net
         if dtype not in ('bf16', 'fp32'):
             raise ValueError("dtype must be 'bf16' (performance) or 'fp32' (parity mode)")
@@ -1414,6 +1420,10 @@ class Engine:
         # label smoothing (TRAIN --label-smoothing) is the second scalar of the same ops, either kind: f[1] != 0 sends the op to the
         # smoothed kernel (ifcbk_softmax_xent_ls); without it f[1] stays the zero of a fresh op and the tables are what they were
         ls = (self.label_smoothing,) if self.label_smoothing > 0 else ()
+        # the focusing exponent (TRAIN --focal-gamma) is the third scalar: f[2] != 0 sends the op to ifcbk_softmax_xent_focal; the
+        # engine refuses the two together, so f[1] is then the zero it writes here
+        if self.focal_gamma > 0:
+            ls = (0.0, self.focal_gamma)
         lossl.add(xent, 'loss', p=(_vp(main.logits), _vp(self.target), _vp(self.loss), _vp(main.dlogits)) + cw,
                   i=(N, net.NC), f=(1.0,) + ls)
         for h in auxh:

@@ -249,6 +249,29 @@ def get_namebrand_model(model_name, num_o_classes, pretrained=False, device=0, m
     return HipBackbone(net, device, max_batch, dtype, **engine_kw)
 
 
+class FocalLoss(nn.Module):
+    """TRAIN --focal-gamma: ``sum_n w[t_n] u_n^gamma (-log p[n][t_n]) / sum_n w[t_n]`` with ``u_n = 1 - p[n][t_n]`` and ``w`` the class weights
+    (None: all ones) -- the function of the engine's fused loss op (``ifcbk_softmax_xent_focal``), with torch ops, for the reference-style
+    ``training_step`` / ``validation_step``.  ``u`` is the softmax mass of the other classes, summed directly: ``1 - p`` cancels when
+    the target is the row's maximum.  The weights are a buffer named ``weight``, the key a weighted ``nn.CrossEntropyLoss`` has."""
+
+    def __init__(self, gamma, weight=None):
+        super().__init__()
+        self.gamma = float(gamma)
+        self.register_buffer('weight', weight)
+
+    def forward(self, logits, target):
+        mx = logits.max(1, keepdim=True).values
+        ex = torch.exp(logits - mx)
+        s = ex.sum(1)
+        oh = torch.zeros_like(ex, dtype=torch.bool).scatter_(1, target[:, None], True)
+        u = ex.masked_fill(oh, 0.0).sum(1) / s
+        li = mx[:, 0] + torch.log(s) - logits.gather(1, target[:, None])[:, 0]
+        wt = torch.ones_like(s) if self.weight is None else self.weight.to(logits.dtype)[target]
+        pw = torch.where(u > 0, u.clamp_min(torch.finfo(u.dtype).tiny).pow(self.gamma), torch.zeros_like(u))
+        return (wt * (pw * li)).sum() / wt.sum()
+
+
 class NeustonModel(nn.Module):
     """``neuston_models.py:48-180`` without Lightning: same hooks, same loss, same optimizer, same
     aggregation.  ``training_step`` / ``validation_step`` / ``test_step`` accept the reference's batch tuples.
@@ -261,19 +284,24 @@ class NeustonModel(nn.Module):
         self.hparams = hparams
         mb = max_batch or getattr(hparams, 'batch_size', None) or 32
         opt = str(getattr(hparams, 'optimizer', None) or 'Adam').lower()
-        # additive (TRAIN --class-norm / --weight-decay / --label-smoothing): per-class loss weights, L2 weight decay and the smoothing
-        # factor of the loss; absent = upstream's behaviour
+        # additive (TRAIN --class-norm / --weight-decay / --label-smoothing / --focal-gamma): per-class loss weights, L2 weight decay, the
+        # smoothing factor and the focusing exponent of the loss; absent = upstream's behaviour
         cw = getattr(hparams, 'class_weights', None)
         ls = float(getattr(hparams, 'label_smoothing', None) or 0.0)
+        fg = float(getattr(hparams, 'focal_gamma', None) or 0.0)
         self.model = get_namebrand_model(hparams.MODEL, len(hparams.classes), hparams.pretrained, device, mb,
                                          getattr(hparams, 'precision', 'bf16') or 'bf16', optimizer=opt,
                                          lr=float(getattr(hparams, 'learning_rate', None) or 0.001),
                                          momentum=float(getattr(hparams, 'momentum', None) or 0.0), train_batch=train_batch,
                                          class_weights=cw, weight_decay=float(getattr(hparams, 'weight_decay', None) or 0.0),
-                                         label_smoothing=ls)
+                                         label_smoothing=ls, focal_gamma=fg)
         # what upstream would have written at neuston_models.py:55; the engine's fused loss ops compute the same weighted, smoothed mean
         eng = self.model.engine
-        self.criterion = nn.CrossEntropyLoss(weight=None if cw is None else eng.class_weight.clone(), label_smoothing=eng.label_smoothing)
+        cwt = None if cw is None else eng.class_weight.clone()
+        if eng.focal_gamma > 0:
+            self.criterion = FocalLoss(eng.focal_gamma, cwt)
+        else:
+            self.criterion = nn.CrossEntropyLoss(weight=cwt, label_smoothing=eng.label_smoothing)
         self.best_val_loss = np.inf
         self.best_epoch = 0
         self.agg_train_loss = 0.0

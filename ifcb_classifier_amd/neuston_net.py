@@ -68,6 +68,23 @@ def _label_smoothing(text):
     return v
 
 
+def _focal_gamma(text):
+    v = float(text)
+    if not 0.0 <= v < float('inf'):            # (nan fails both comparisons)
+        raise argparse.ArgumentTypeError('GAMMA must be finite and not negative, got %r' % text)
+    return v
+
+
+class _ExclusiveLossScalar(argparse.Action):
+    """stores --label-smoothing / --focal-gamma; the second of the two to arrive non-zero is an argparse error naming both"""
+    FLAGS = {'label_smoothing': '--label-smoothing', 'focal_gamma': '--focal-gamma'}
+
+    def __call__(self, parser, namespace, value, option_string=None):
+        setattr(namespace, self.dest, value)
+        if all(getattr(namespace, d, 0.0) for d in self.FLAGS):
+            parser.error('%s and %s do not combine: give one of them' % tuple(sorted(self.FLAGS.values(), reverse=True)))
+
+
 def _dist():
     import torch.distributed as dist
     if int(os.environ.get('WORLD_SIZE', 1)) > 1:
@@ -574,7 +591,8 @@ def argparse_nn_train(train_subparser):
     optim.add_argument('--momentum', default=0.0, type=float, help='SGD momentum. Default is 0')
     optim.add_argument('--weight-decay', default=0.0, type=float, help='L2 weight decay of every parameter, as torch.optim.Adam/SGD(weight_decay=WD) (not AdamW). Default is 0')
     optim.add_argument('--class-norm', metavar='POWER', nargs='?', const=1.0, type=_class_norm_power, default=None, help='Bias results to emphasize smaller classes: weight the loss of class c by n_c^-POWER (n_c: training images of the class), scaled to a mean weight of 1 per training image. POWER defaults to 1 ("balanced"); 0 weights all classes equally. Default (unset) is the unweighted loss')
-    optim.add_argument('--label-smoothing', metavar='EPS', default=0.0, type=_label_smoothing, help='Label smoothing of the loss, as nn.CrossEntropyLoss(label_smoothing=EPS): the target distribution is (1-EPS) one-hot + EPS/C uniform, for noisy annotations. A float in [0, 1]; val_loss follows the smoothed value. Default is 0 (hard labels)')
+    optim.add_argument('--label-smoothing', metavar='EPS', default=0.0, type=_label_smoothing, action=_ExclusiveLossScalar, help='Label smoothing of the loss, as nn.CrossEntropyLoss(label_smoothing=EPS): the target distribution is (1-EPS) one-hot + EPS/C uniform, for noisy annotations. A float in [0, 1]; val_loss follows the smoothed value. Default is 0 (hard labels)')
+    optim.add_argument('--focal-gamma', metavar='GAMMA', default=0.0, type=_focal_gamma, action=_ExclusiveLossScalar, help='Focal loss against class imbalance: the loss of an image is scaled by (1 - p)^GAMMA, p the softmax probability of its class, so images the network already classifies confidently count less. A finite float >= 0; composes with --class-norm (its weights are the per-class alpha), not with --label-smoothing; val_loss follows the focal value. Default is 0 (cross-entropy)')
     meta = t.add_argument_group(title='Metadata and Annotations')
     meta.add_argument('--dataset-id', help='Associate a dataset id label with this model')
     meta.add_argument('--notes', help='Add any kind of note to the trained model.')

@@ -237,6 +237,18 @@ IFCBK_API int ifcbk_softmax_xent_w(ifcbk_ctx*, const float* logits, const int64_
 IFCBK_API int ifcbk_softmax_xent_ls(ifcbk_ctx*, const float* logits, const int64_t* target, const float* class_weight /*nullable*/, int N,
                           int NC, float weight, float label_smoothing, float* loss_out, int loss_accumulate,
                           float* dlogits /*nullable*/, void* stream);
+/* focal loss (TRAIN --focal-gamma) on the same operands.  p = softmax(logits), w = class_weight (NULL = all ones), W = sum_i w[target_i],
+ * u_i = 1 - p_i[target_i], L_i = -log p_i[target_i]:
+ * loss_out[0] (+)= weight / W * sum_i w[target_i] u_i^gamma L_i;
+ * dlogits_i[j] = weight / W * w[target_i] (p_i[j] - [j == target_i]) (u_i^gamma + gamma p_i[target_i] u_i^(gamma - 1) L_i).
+ * The normaliser is W, as above: gamma -> 0 is ifcbk_softmax_xent_w's function (gamma = 0 is legal: that function, not its bits), and
+ * class_weight acts as focal loss's per-class alpha.  u is formed as (sum_{j != target} exp) / (sum_j exp), never as 1 - p; a row with
+ * u == 0 in fp32 gives a loss term of 0 and a zero dlogits row for gamma > 0 (always so when NC == 1).
+ * IFCBK_EINVAL: gamma negative or not finite, N or NC < 1, NULL logits / target / loss_out.  One block, fixed summation order: bitwise
+ * reproducible.                                                                                                                      */
+IFCBK_API int ifcbk_softmax_xent_focal(ifcbk_ctx*, const float* logits, const int64_t* target, const float* class_weight /*nullable*/, int N,
+                          int NC, float weight, float gamma, float* loss_out, int loss_accumulate, float* dlogits /*nullable*/,
+                          void* stream);
 /* the bookkeeping of one fused train step, in the step's own op table (no framework kernel between the first and the last
  * launch of a step): num_batches_tracked[0..n) += 1 of every BatchNorm ([PL]/torch: nn.BatchNorm2d.forward in training) and
  * loss_sum += loss (the reference's train_loss is the SUM of the batch losses, neuston_models.py:85).  Either part may be NULL. */
@@ -410,7 +422,9 @@ enum {
     IFCBK_OP_SOFTMAX_XENT_W  /* p: logits, target, loss, dlogits (nullable), class_weight; i: N, NC; f[0] = weight; flags bit 0 accumulate.
                               * f[1] = label smoothing factor, for this kind and for IFCBK_OP_SOFTMAX_XENT (p: logits, target, loss, dlogits
                               * (nullable); i: N, NC; f[0] = weight): 0, what a zeroed op holds, is the unsmoothed call; any other value
-                              * runs ifcbk_softmax_xent_ls with the same operands (class_weight = p[4] here, NULL for the plain kind)   */
+                              * runs ifcbk_softmax_xent_ls with the same operands (class_weight = p[4] here, NULL for the plain kind).
+                              * f[2] = focal-loss gamma, for the same two kinds: 0 is today's call; any other value runs
+                              * ifcbk_softmax_xent_focal with the same operands; f[1] != 0 together with f[2] != 0 is IFCBK_EINVAL      */
 };
 typedef struct {
     ifcbk_conv_desc d;
