@@ -152,6 +152,8 @@ _PROTOS = {
     'ifcbk_roi_preprocess_workspace': (_sz, [C.POINTER(RoiDesc), _i, _i]),
     'ifcbk_roi_preprocess_fit': (_i, [_vp, C.POINTER(RoiDesc), _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     'ifcbk_roi_preprocess_fit_workspace': (_sz, [C.POINTER(RoiDesc), _i, _i]),
+    'ifcbk_roi_jitter': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    'ifcbk_roi_jitter_workspace': (_sz, [_i]),
     'ifcbk_u8_channel_moments': (_i, [_vp, _vp, _i, C.c_int64, _i, _vp, _vp]),
     'ifcbk_stem_u8_rows': (_i, [C.POINTER(ConvDesc)]),
     'ifcbk_stem_u8_fwd': (_i, [_vp, C.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),

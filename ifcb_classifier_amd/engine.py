@@ -1711,19 +1711,24 @@ class Engine:
         self.in_kind[self.in_slot] = 'nhwc'
         return N
 
-    def load_rois(self, pixels, offs, hs, ws, max_h, max_w, in_channels=1, flips=None, mean=None, std=None, slot=None, turn=False, pad=None):
+    def load_rois(self, pixels, offs, hs, ws, max_h, max_w, in_channels=1, flips=None, mean=None, std=None, slot=None, turn=False, pad=None,
+                  jitter=None):
         """ragged u8 ROIs (device tensors) -> input buffer via the PIL-exact resize kernel.  slot: the input slot of a
         prefetch (runs on the prefetch stream with the prefetch context's workspace); None = the current slot, current stream.
         turn: the codes in ``flips`` may hold bit 2 = transpose (TRAIN --rot90; neuston_data.fold_turns).
         pad: None = squash to S x S (ifcbk_roi_preprocess); 'border' or a level 0..255 = keep the aspect ratio and fill the rest
-        (TRAIN --pad; ifcbk_roi_preprocess_fit)."""
+        (TRAIN --pad; ifcbk_roi_preprocess_fit).
+        jitter: None, or (brightness, contrast): float32 device tensors of one factor per ROI, either may be None (TRAIN --jitter).
+        ifcbk_roi_jitter then maps the ROIs IN PLACE ahead of the resize, on the same ctx and stream: ``pixels`` is overwritten
+        with the jittered ROIs."""
         if slot is not None:
             return self._load_rois_into(self.pre_ctx, C.c_void_p(self.pre_stream.cuda_stream), slot, False,
-                                        pixels, offs, hs, ws, max_h, max_w, in_channels, flips, mean, std, turn, pad)
+                                        pixels, offs, hs, ws, max_h, max_w, in_channels, flips, mean, std, turn, pad, jitter)
         return self._load_rois_into(self.ctx, self.stream(), self.in_slot, True, pixels, offs, hs, ws, max_h,
-                                    max_w, in_channels, flips, mean, std, turn, pad)
+                                    max_w, in_channels, flips, mean, std, turn, pad, jitter)
 
-    def _load_rois_into(self, ctx, stream, slot, main, pixels, offs, hs, ws, max_h, max_w, in_channels, flips, mean, std, turn=False, pad=None):
+    def _load_rois_into(self, ctx, stream, slot, main, pixels, offs, hs, ws, max_h, max_w, in_channels, flips, mean, std, turn=False, pad=None,
+                        jitter=None):
         n = hs.numel()
         dst = self.in_bufs[slot]
         d = RoiDesc()
@@ -1742,6 +1747,14 @@ class Engine:
         else:
             fn, fill = 'ifcbk_roi_preprocess_fit', (pad_fill(pad),)
         need = getattr(ctx.lib, fn + '_workspace')(C.byref(d), int(max_h), int(max_w))
+        if jitter is not None and jitter[0] is None and jitter[1] is None:
+            jitter = None
+        if jitter is not None:
+            for f in jitter:
+                if f is not None and not (torch.is_tensor(f) and f.dtype == torch.float32 and f.device == pixels.device and f.numel() == n
+                                          and f.is_contiguous()):
+                    raise ValueError('jitter: (brightness, contrast) are float32 tensors of %d factors on %s, or None' % (n, pixels.device))
+            need = max(need, ctx.lib.ifcbk_roi_jitter_workspace(n))
         if need > ctx.lib.ifcbk_ctx_workspace_bytes(ctx.h):
             if not main:
                 self.pre_stream.synchronize()        # an earlier prefetch may still read the arena that is about to move
@@ -1751,6 +1764,10 @@ class Engine:
                     for g in pl.graphs.values():
                         self.ctx.lib.ifcbk_graph_destroy(self.ctx.h, g)
                     pl.graphs.clear()
+        if jitter is not None:
+            # in place on the uploaded blob, stream-ordered in front of the resize (its sums lie where the resize puts its tables)
+            ctx.call('ifcbk_roi_jitter', _vp(pixels), _vp(offs), _vp(hs), _vp(ws), n, int(in_channels), int(max_h), int(max_w),
+                     _vp(jitter[0]), _vp(jitter[1]), _vp(pixels), stream)
         if self.stem_u8 is not None and in_channels == 1:
             # grey ROIs: only the resized u8 plane is written; x_c = a_c * g + b_c (ToTensor, Normalize, transform_input) goes to the
             # stem conv as six floats

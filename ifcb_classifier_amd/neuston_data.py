@@ -33,8 +33,9 @@ def default_loader(path):
 class RoiTransform:
     """What ``transforms.Compose([flips] + [Resize, ToTensor, Normalize?])`` means on the GPU path."""
 
-    def __init__(self, resize, img_norm=None, vflip=False, hflip=False, rot90=False, pad=None):
+    def __init__(self, resize, img_norm=None, vflip=False, hflip=False, rot90=False, pad=None, jitter=None):
         self.resize = resize
+        self.jitter = parse_jitter(jitter)   # --jitter: None, or [B, C] = the brightness / contrast ranges of ColorJitter (not both 0)
         self.pad = parse_pad(pad)         # --pad: None = squash to resize x resize, 'border' / 0..255 = keep the aspect ratio, fill the rest
         self.img_norm = img_norm          # (mean[3], std[3]) or None
         self.vflip, self.hflip = vflip, hflip
@@ -52,6 +53,42 @@ class RoiTransform:
         if self.rot90:
             code = fold_turns(code & 1, code >> 1, random.randrange(4))
         return code
+
+    def jitter_factors(self):
+        """(fb, fc) of ``ColorJitter(brightness=B, contrast=C)``: each uniform in [max(0, 1 - range), 1 + range], rounded to float32;
+        None for a zero range, which draws nothing.  Called after ``flip_code``: brightness first, then contrast.  The order of the
+        two enhancements is always brightness, contrast (torchvision permutes them at random)."""
+        if self.jitter is None:
+            return None, None
+        return tuple(float(np.float32(random.uniform(max(0.0, 1.0 - r), 1.0 + r))) if r > 0 else None for r in self.jitter)
+
+
+def parse_jitter(value):
+    """``--jitter B[,C]`` / a checkpoint's ``jitter``: None, a 'B' / 'B,C' string or a (B, C) pair -> None (unset, also for 0 and 0,0) or
+    [B, C], finite floats >= 0 (C defaults to 0)"""
+    if value is None:
+        return None
+    if isinstance(value, str):
+        parts = value.split(',')
+    elif isinstance(value, (list, tuple)):
+        parts = list(value)
+    else:
+        parts = [value]
+    if not 1 <= len(parts) <= 2 or any(isinstance(v, bool) for v in parts):
+        raise ValueError('jitter: B[,C] expected, got %r' % (value,))
+    bc = [float(v) for v in parts] + [0.0] * (2 - len(parts))           # (float('a') raises ValueError too)
+    if not all(0.0 <= v < float('inf') for v in bc):                   # (nan fails both comparisons)
+        raise ValueError('jitter: B and C must be finite and not negative, got %r' % (value,))
+    return bc if any(bc) else None
+
+
+def jitter_arg(text):
+    """argparse ``type=`` of ``--jitter B[,C]`` (neuston_net TRAIN)"""
+    import argparse
+    try:
+        return parse_jitter(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError('B[,C] must be one or two finite floats >= 0, got %r' % text)
 
 
 def parse_pad(value):
@@ -258,6 +295,9 @@ class NeustonDataset(Dataset):
         path = self.images[index]
         data = default_loader(path)
         flip = self.transforms.flip_code() if self.transforms is not None else 0
+        if self.transforms is not None and getattr(self.transforms, 'jitter', None) is not None:
+            # (fields four and five: the brightness and contrast factors of this draw, None for a zero range)
+            return (data, flip, bool(getattr(self.transforms, 'rot90', False))) + self.transforms.jitter_factors(), self.targets[index], path
         if self.transforms is not None and getattr(self.transforms, 'rot90', False):
             return (data, flip, True), self.targets[index], path      # (third field: the transform turns, whatever this draw was)
         return (data, flip), self.targets[index], path
@@ -318,7 +358,8 @@ def get_trainval_transforms(args):
     vflip, hflip = 'x' in flip, 'y' in flip                # 'x' = vertical, 'y' = horizontal (sic)
     rot90 = getattr(args, 'rot90', None)                   # None (unset) | 'T' (training set) | '+V' (validation set as well)
     pad = getattr(args, 'pad', None)                       # geometry, not augmentation: both sets alike
-    train = RoiTransform(args.resize, norm, vflip, hflip, rot90=bool(rot90), pad=pad)
+    jitter = getattr(args, 'jitter', None)                 # photometric augmentation: the training set only
+    train = RoiTransform(args.resize, norm, vflip, hflip, rot90=bool(rot90), pad=pad, jitter=jitter)
     val = RoiTransform(args.resize, norm, vflip and '+V' in flip, hflip and '+V' in flip, rot90=rot90 == '+V', pad=pad)
     return train, val
 
@@ -373,9 +414,11 @@ class IfcbBinDataset(Dataset):
 
 # ------------------------------------------------------------------------------------------ batching
 def collate_rois(items):
-    """DataLoader collate_fn: [( (img_u8, flip[, turn]), *rest )] -> (roi_batch dict, *rest lists).  One ragged u8 blob,
+    """DataLoader collate_fn: [( (img_u8, flip[, turn[, fb, fc]]), *rest )] -> (roi_batch dict, *rest lists).  One ragged u8 blob,
     an int64 offset table and int32 dims; tensors are pinned by the loader (pin_memory=True).  ``turn`` (items of a dataset whose
-    transform has rot90 set) marks the batch for the quarter-turn kernels whatever codes were drawn."""
+    transform has rot90 set) marks the batch for the quarter-turn kernels whatever codes were drawn.  ``fb`` / ``fc`` (items of a
+    dataset whose transform has jitter set) become float32 ``brightness`` / ``contrast`` tensors, each present only when some item
+    carries that factor (an item without it counts as 1)."""
     imgs = [it[0][0] for it in items]
     flips = [it[0][1] for it in items]
     turn = any(len(it[0]) > 2 and it[0][2] for it in items)
@@ -393,6 +436,9 @@ def collate_rois(items):
                  max_h=int(hs.max()), max_w=int(ws.max()), in_channels=ch)
     if turn:
         batch['turn'] = True
+    for key, k in (('brightness', 3), ('contrast', 4)):
+        if any(len(it[0]) > k and it[0][k] is not None for it in items):
+            batch[key] = torch.tensor([it[0][k] if len(it[0]) > k and it[0][k] is not None else 1.0 for it in items], dtype=torch.float32)
     rest = list(zip(*[it[1:] for it in items]))
     out = [batch]
     for r in rest:
@@ -402,7 +448,8 @@ def collate_rois(items):
 
 
 def rois_to_device(batch, device, transform=None):
-    """upload a collated ROI batch (u8 blob + tables) and attach Normalize parameters and the transform's ``pad`` (when set)."""
+    """upload a collated ROI batch (u8 blob + tables) and attach Normalize parameters, the transform's ``pad`` (when set) and the
+    batch's jitter factors (when it carries any): ``jitter=(brightness, contrast)``, device tensors or None."""
     kw = dict(pixels=batch['pixels'].to(device, non_blocking=True), offs=batch['offs'].to(device, non_blocking=True),
               hs=batch['hs'].to(device, non_blocking=True), ws=batch['ws'].to(device, non_blocking=True),
               max_h=batch['max_h'], max_w=batch['max_w'], in_channels=batch['in_channels'])
@@ -416,4 +463,6 @@ def rois_to_device(batch, device, transform=None):
         kw['mean'], kw['std'] = transform.img_norm
     if transform is not None and getattr(transform, 'pad', None) is not None:
         kw['pad'] = transform.pad
+    if 'brightness' in batch or 'contrast' in batch:
+        kw['jitter'] = tuple(batch[k].to(device, non_blocking=True) if k in batch else None for k in ('brightness', 'contrast'))
     return kw

@@ -364,6 +364,8 @@ class NeustonModel(nn.Module):
     # engine's other input slot while the current step runs (Engine.prefetch_begin / prefetch_end / use_prefetched):
     #     n = model.stage_batch(first);  for each batch: model.use_staged(); n2 = model.stage_batch(next); model.fit_current(n)
     def stage_batch(self, rois, transform=None, input_classes=None):
+        """upload and preprocess a collated batch into the prefetch slot; jitter factors the batch carries (TRAIN --jitter) go along in
+        ``rois_to_device``'s kwargs, as they do through ``fit_batch(rois_to_device(...), ...)``"""
         from .neuston_data import rois_to_device
         eng = self.model.engine
         slot, side = eng.prefetch_begin()

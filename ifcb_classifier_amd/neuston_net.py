@@ -21,7 +21,7 @@ from torch.utils.data import DataLoader
 
 from .neuston_callbacks import SaveValidationResults, SaveTestResults
 from .neuston_data import (get_trainval_datasets, IfcbBinDataset, ImageDataset, IMG_EXTENSIONS, collate_rois,
-                           pad_arg, rois_to_device)
+                           jitter_arg, pad_arg, rois_to_device)
 from .neuston_models import NeustonModel, load_checkpoint_file, load_pretrained_weights
 
 
@@ -578,6 +578,7 @@ def argparse_nn_train(train_subparser):
     augs = t.add_argument_group(title='Augmentation Options')
     augs.add_argument('--flip', choices=['x', 'y', 'xy', 'x+V', 'y+V', 'xy+V'], help='Training images have 50%% chance of being flipped along the designated axis: (x) vertically, (y) horizontally, (xy) either/both. "+V" includes the Validation dataset')
     augs.add_argument('--rot90', nargs='?', const='T', choices=['T', '+V'], default=None, help='(MI355X path, additive) Training images are rotated counter-clockwise by k quarter turns, k uniform in {0,1,2,3}, after any --flip and before the resize. "+V" includes the Validation dataset. With "--flip xy" the eight symmetries of the square are equally likely. Default (unset) is no rotation')
+    augs.add_argument('--jitter', metavar='B[,C]', type=jitter_arg, default=None, help='(MI355X path, additive) Brightness / contrast jitter of the training images, as transforms.ColorJitter(brightness=B, contrast=C) in front of the resize: per image a brightness factor uniform in [max(0, 1-B), 1+B] and a contrast factor uniform in [max(0, 1-C), 1+C] (PIL.ImageEnhance arithmetic, on the GPU; always brightness first). B and C are finite floats >= 0, C defaults to 0. Training set only. Default (unset, also "0") is no jitter')
     out = t.add_argument_group(title='Output Options')
     out.add_argument('--outdir', default='training-output/{TRAIN_ID}', help='Default is "training-output/{TRAIN_ID}"')
     out.add_argument('--model-id', default='{TRAIN_ID}', help='Set a specific model id. Patterns {TRAIN_DATE} and {TRAIN_ID} are recognized. Default is "{TRAIN_ID}"')

@@ -296,6 +296,21 @@ IFCBK_API int ifcbk_roi_preprocess_fit(ifcbk_ctx*, const ifcbk_roi_desc*, const 
                          const int32_t* hs, const int32_t* ws, const uint8_t* codes, int max_h, int max_w,
                          int fill /* 0..255, or -1 = border */, void* out, uint8_t* out_u8, void* stream);
 IFCBK_API size_t ifcbk_roi_preprocess_fit_workspace(const ifcbk_roi_desc*, int max_h, int max_w);
+/* Brightness / contrast jitter of the ragged u8 ROIs themselves (TRAIN --jitter), ahead of either resize call: per ROI i
+ *   img' = ImageEnhance.Contrast(ImageEnhance.Brightness(img).enhance(brightness[i])).enhance(contrast[i])      (Pillow)
+ * i.e. the table lut[v] = clip(trunc(fl32(fl32(m) + fl32(f * fl32(v - m))))), m = 0 for brightness and, for contrast, the rounded
+ * mean (2 sum L + n) / (2 n) of the L plane after the brightness step (one channel: L = v; three: L = (19595 R + 38470 G + 7471 B +
+ * 0x8000) >> 16; the same table for every channel).  Either factor array may be NULL (= all 1), not both; a factor that is
+ * negative or not finite counts as 1.  pixels / offs / hs / ws / in_channels / max_h / max_w as ifcbk_roi_preprocess; out has the
+ * layout of pixels and may be pixels itself: only the bytes [offs[i], offs[i] + h * w * in_channels) of each ROI are written.
+ * With contrast the ctx workspace holds the per-ROI sums (ifcbk_roi_jitter_workspace bytes; the resize call that follows on the
+ * same stream may reuse it).  Results are reproducible bit for bit.  n_img < 1, in_channels other than 1 / 3, a NULL pixels, offs,
+ * hs, ws or out and two NULL factor arrays are IFCBK_EINVAL. */
+IFCBK_API size_t ifcbk_roi_jitter_workspace(int n_img);
+IFCBK_API int ifcbk_roi_jitter(ifcbk_ctx*, const uint8_t* pixels, const int64_t* offs, const int32_t* hs, const int32_t* ws,
+                         int n_img, int in_channels /*1|3*/, int max_h, int max_w,
+                         const float* brightness /*[n_img], nullable*/, const float* contrast /*[n_img], nullable*/,
+                         uint8_t* out /* same layout as pixels; may be == pixels */, void* stream);
 /* per-image, per-channel integer moments of a u8 plane [n_img][pixels_per_img][channels] (channels 1..4):
    out[i][c][0] = sum of v, out[i][c][1] = sum of v*v, exact (uint64); n_img = 0 is a no-op.
  * x is typically out_u8 of ifcbk_roi_preprocess; mean = sum v / (255 n), population std from the two sums.
