@@ -1,7 +1,8 @@
 // Class-weighted cross-entropy: nn.CrossEntropyLoss(weight=w), mean reduction (TRAIN --class-norm).  The unweighted loss keeps its
 // own kernel and entry point (pool_head.hip); this file is reached only when the engine holds class weights -- or a label-smoothing
 // factor (TRAIN --label-smoothing: softmax_xent_ls_kernel, with or without class weights), or a focusing exponent (TRAIN --focal-gamma:
-// softmax_xent_focal_kernel, with or without class weights).
+// softmax_xent_focal_kernel, with or without class weights), or the factors of a mixed batch (TRAIN --mixup / --cutmix:
+// softmax_xent_mix_kernel, two targets per image, with or without class weights and smoothing).
 #include "common.h"
 #include <float.h>
 #include <math.h>
@@ -239,6 +240,96 @@ __global__ __launch_bounds__(1024) void softmax_xent_focal_kernel(const float* l
     }
 }
 
+// Two-target loss of a mixed batch (TRAIN --mixup / --cutmix; ifcbk_batch_mix pairs image n with m = N - 1 - n): with a = target[n],
+// b = target[N - 1 - n], lam_n = lam[n], p = softmax(l), w = class_weight (NULL: all ones), c1 = 1 - eps, eC = eps / NC, SW = sum_k w[k]:
+//   h_n     = lam_n w[a] + (1 - lam_n) w[b],    W = sum_n h_n
+//   loss    = weight / W * sum_n [ c1 (lam_n w[a] (-log p[n][a]) + (1 - lam_n) w[b] (-log p[n][b])) + eC sum_j w[j] (-log p[n][j]) ]
+//   d[n][j] = weight / W * [ (c1 h_n + eC SW) p[n][j] - c1 lam_n w[a] [j == a] - c1 (1 - lam_n) w[b] [j == b] - eC w[j] ]
+// Without weights W == N and this is timm's SoftTargetCrossEntropy on mixup_target; at lam == 1 it is softmax_xent_ls_kernel's function
+// (eps == 0: softmax_xent_w_kernel's), through this kernel's own operations.  a == b is legal: both one-hot terms land on one element.
+// softmax_xent_ls_kernel's shape: one 1024-thread block, 4 lanes per sample, fixed butterflies, one fixed-order slot pre-pass for W and
+// SW, fixed-order final sum -- bitwise reproducible; the smoothing term is summed from the same non-negative pieces.  Per sample, on top
+// of that kernel: 1 - lam_n, two products and an add for h_n (computed the same way in the pre-pass and in the row), a second -log p.
+// A target outside [0, NC) or a lam outside [0, 1] is the caller's fault; so is W == 0.
+__global__ __launch_bounds__(1024) void softmax_xent_mix_kernel(const float* logits, const int64_t* target, const float* lam,
+                                                                const float* class_weight, int N, int NC, float weight, float eps,
+                                                                float* loss_out, int loss_acc, float* dlogits) {
+    __shared__ float sl[256];
+    __shared__ float sk[256];
+    __shared__ float sW[2];
+    const int sub = threadIdx.x & 3, slot = threadIdx.x >> 2;
+    if (sub == 0) {
+        float wsum = 0.f, ksum = 0.f;
+        for (int n = slot; n < N; n += 256) {
+            const float lm = lam[n];
+            const float ta = lm * (class_weight ? class_weight[(int)target[n]] : 1.f);
+            const float tb = (1.f - lm) * (class_weight ? class_weight[(int)target[N - 1 - n]] : 1.f);
+            wsum += ta + tb;
+        }
+        for (int k = slot; k < NC; k += 256) ksum += class_weight ? class_weight[k] : 1.f;
+        sl[slot] = wsum;
+        sk[slot] = ksum;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float s = 0.f, k = 0.f;
+        for (int i = 0; i < 256; ++i) s += sl[i];
+        for (int i = 0; i < 256; ++i) k += sk[i];
+        sW[0] = s;
+        sW[1] = k;
+    }
+    __syncthreads();
+    const float W = sW[0], SW = sW[1];
+    const float invW = 1.f / W;
+    const float g = weight / W;
+    const float c1 = 1.f - eps, eC = eps / (float)NC;
+    float local = 0.f;
+    for (int n0 = 0; n0 < N; n0 += 256) {
+        const int n = n0 + slot;
+        const bool ok = n < N;
+        const float* l = logits + (size_t)(ok ? n : 0) * NC;
+        float mx = -INFINITY;
+        for (int j = sub; j < NC; j += 4) mx = fmaxf(mx, l[j]);
+        mx = fmaxf(mx, __shfl_xor(mx, 1));
+        mx = fmaxf(mx, __shfl_xor(mx, 2));
+        float s = 0.f;
+        for (int j = sub; j < NC; j += 4) s += expf(l[j] - mx);
+        s += __shfl_xor(s, 1);
+        s += __shfl_xor(s, 2);
+        const float ls = logf(s);
+        float q = 0.f;
+        for (int j = sub; j < NC; j += 4) q += (class_weight ? class_weight[j] : 1.f) * ((mx - l[j]) + ls);
+        q += __shfl_xor(q, 1);
+        q += __shfl_xor(q, 2);
+        const int ta_i = ok ? (int)target[n] : 0, tb_i = ok ? (int)target[N - 1 - n] : 0;
+        const float lm = ok ? lam[n] : 1.f;
+        const float ta = ok ? lm * (class_weight ? class_weight[ta_i] : 1.f) : 0.f;
+        const float tb = ok ? (1.f - lm) * (class_weight ? class_weight[tb_i] : 1.f) : 0.f;
+        const float h = ta + tb;
+        if (ok && sub == 0) {
+            const float lia = mx + ls - l[ta_i], lib = mx + ls - l[tb_i];
+            local += c1 * (ta * lia + tb * lib) + eC * q;
+        }
+        if (ok && dlogits) {
+            float* d = dlogits + (size_t)n * NC;
+            const float is = 1.f / s;
+            const float ha = c1 * ta, hb = c1 * tb;
+            const float A = c1 * h + eC * SW;
+            for (int j = sub; j < NC; j += 4)
+                d[j] = g * (A * (expf(l[j] - mx) * is) - (j == ta_i ? ha : 0.f) - (j == tb_i ? hb : 0.f) - eC * (class_weight ? class_weight[j] : 1.f));
+        }
+    }
+    __syncthreads();                       // (thread 0 has finished reading the pre-pass partials)
+    if (sub == 0) sl[slot] = local;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float s = 0.f;
+        for (int i = 0; i < 256; ++i) s += sl[i];
+        s = s * invW * weight;
+        loss_out[0] = loss_acc ? loss_out[0] + s : s;
+    }
+}
+
 }  // namespace
 
 #define ST ((hipStream_t)stream)
@@ -274,5 +365,18 @@ extern "C" int ifcbk_softmax_xent_focal(ifcbk_ctx* ctx, const float* logits, con
     hipLaunchKernelGGL(softmax_xent_focal_kernel, dim3(1), dim3(1024), 0, ST, logits, target, class_weight, N, NC, weight, gamma, loss_out,
                        loss_accumulate, dlogits);
     IFCBK_LAUNCH_CHECK(ctx, "softmax_xent_focal");
+    return IFCBK_OK;
+}
+
+extern "C" int ifcbk_softmax_xent_mix(ifcbk_ctx* ctx, const float* logits, const int64_t* target, const float* lam, const float* class_weight,
+                                      int N, int NC, float weight, float label_smoothing, float* loss_out, int loss_accumulate,
+                                      float* dlogits, void* stream) {
+    if (N <= 0 || NC <= 0) IFCBK_FAIL(ctx, IFCBK_EINVAL, "softmax_xent_mix: empty");
+    if (!lam) IFCBK_FAIL(ctx, IFCBK_EINVAL, "softmax_xent_mix: lam is NULL (the one-target losses are ifcbk_softmax_xent_w / _ls)");
+    if (!(label_smoothing >= 0.f && label_smoothing <= 1.f)) IFCBK_FAIL(ctx, IFCBK_EINVAL, "softmax_xent_mix: label_smoothing outside [0, 1]");
+    if (!logits || !target || !loss_out) IFCBK_FAIL(ctx, IFCBK_EINVAL, "softmax_xent_mix: NULL operand");
+    hipLaunchKernelGGL(softmax_xent_mix_kernel, dim3(1), dim3(1024), 0, ST, logits, target, lam, class_weight, N, NC, weight, label_smoothing,
+                       loss_out, loss_accumulate, dlogits);
+    IFCBK_LAUNCH_CHECK(ctx, "softmax_xent_mix");
     return IFCBK_OK;
 }

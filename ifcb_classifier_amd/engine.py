@@ -181,7 +181,7 @@ class Engine:
 
     def __init__(self, net, device=0, max_batch=32, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, dtype='bf16', optimizer='adam',
                  momentum=0.0, plan_only=False, train_batch=None, dp_world=None, class_weights=None, weight_decay=0.0,
-                 label_smoothing=0.0, focal_gamma=0.0):
+                 label_smoothing=0.0, focal_gamma=0.0, mix=False):
         # dp_world: world size of the data-parallel job this replica belongs to (None: WORLD_SIZE of the launcher, else an
         # initialised torch.distributed group, else 1) -- it picks the program-lane default, and train_step_ddp checks it
         self._dp_world_arg = None if dp_world is None else int(dp_world)
@@ -215,6 +215,11 @@ class Engine:
             raise ValueError('focal_gamma must be finite and not negative')
         if self.focal_gamma > 0 and self.label_smoothing > 0:
             raise ValueError('focal_gamma and label_smoothing do not combine: give one of them')
+        # additive (TRAIN --mixup / --cutmix): the train loss ops read per-image mix factors from a device array (mix_lam) and run the
+        # two-target kernel; mix_batch() mixes a loaded batch with its reverse.  False: buffers, plans and launches are what they were
+        self.mix = bool(mix)
+        if self.mix and self.focal_gamma > 0:
+            raise ValueError('mix and focal_gamma do not combine: give one of them')
         self.net = net
         if dtype not in ('bf16', 'fp32'):
             raise ValueError("dtype must be 'bf16' (performance) or 'fp32' (parity mode)")
@@ -607,6 +612,10 @@ class Engine:
         self.loss_sum = torch.zeros(1, dtype=torch.float32, device=dev)
         # per-class loss weights: one fp32 [NC] tensor, read by the loss ops only (never written by a program)
         self.class_weight = None if self._class_weights_arg is None else torch.tensor(self._class_weights_arg, dtype=torch.float32, device=dev)
+        if self.mix:
+            # one factor per image and input slot, 1 = unmixed; the loss ops of a slot's plans (and the graphs captured from them) hold
+            # the array's address, which is why the factors live on the device and not in the ops' f[]
+            self.mix_lam = [torch.ones(N, dtype=torch.float32, device=dev) for _ in range(2)]
         # workspace: wgrad split-K slabs / bn_bwd partials
         ws = 1 << 20
         for n in self.convs:
@@ -1424,10 +1433,13 @@ class Engine:
         # engine refuses the two together, so f[1] is then the zero it writes here
         if self.focal_gamma > 0:
             ls = (0.0, self.focal_gamma)
-        lossl.add(xent, 'loss', p=(_vp(main.logits), _vp(self.target), _vp(self.loss), _vp(main.dlogits)) + cw,
+        # the factors of a mixed batch (TRAIN --mixup / --cutmix) are a sixth operand of the TRAIN loss ops: p[5] != NULL sends the op to
+        # ifcbk_softmax_xent_mix; the validation loss below stays the one-target loss.  Without mix the tuples are what they were
+        mx = ((None,) * (1 - len(cw)) + (_vp(self.mix_lam[self.in_slot]),)) if self.mix else ()
+        lossl.add(xent, 'loss', p=(_vp(main.logits), _vp(self.target), _vp(self.loss), _vp(main.dlogits)) + cw + mx,
                   i=(N, net.NC), f=(1.0,) + ls)
         for h in auxh:
-            lossl.add(xent, 'loss_aux', p=(_vp(h.logits), _vp(self.target), _vp(self.loss), _vp(h.dlogits)) + cw,
+            lossl.add(xent, 'loss_aux', p=(_vp(h.logits), _vp(self.target), _vp(self.loss), _vp(h.dlogits)) + cw + mx,
                       i=(N, net.NC), f=(0.4,) + ls, flags=1)
         pl.loss = Program(lossl)
         evl = OpList()
@@ -1784,6 +1796,36 @@ class Engine:
         ctx.call(fn, C.byref(d), _vp(pixels), _vp(offs), _vp(hs), _vp(ws), _vp(flips),
                  int(max_h), int(max_w), *fill, _vp(dst), None, stream)
         self.in_kind[slot] = 'nhwc'
+        return n
+
+    def mix_batch(self, n, lam, box=None, slot=None):
+        """mix the ``n`` loaded images of an input slot with their reverse, in place (TRAIN --mixup / --cutmix; timm's Mixup, batch mode):
+        image i becomes lam[i] x[i] + (1 - lam[i]) x[n - 1 - i] outside ``box`` and x[n - 1 - i] inside it, and the factors go to the
+        slot's ``mix_lam``, which the train loss ops read.  lam: a float32 device tensor of n factors in [0, 1], or a python float for
+        all n.  box: None (no cut) or (y0, y1, x0, x1) in pixels of the S x S input.  slot: as ``load_rois`` -- None is the current
+        slot on the current stream, a prefetch slot runs on the prefetch stream and context, right behind its resize."""
+        if not self.mix:
+            raise RuntimeError('mix_batch: this engine was built without mix=True')
+        n = int(n)
+        if not 1 <= n <= self.max_batch:
+            raise ValueError('mix_batch: n %d outside 1..%d' % (n, self.max_batch))
+        if slot is not None:
+            ctx, stream, tstream, s = self.pre_ctx, C.c_void_p(self.pre_stream.cuda_stream), self.pre_stream, slot
+        else:
+            ctx, stream, tstream, s = self.ctx, self.stream(), torch.cuda.current_stream(self.dev), self.in_slot
+        y0, y1, x0, x1 = (0, 0, 0, 0) if box is None else (int(v) for v in box)
+        with torch.cuda.stream(tstream):
+            if torch.is_tensor(lam):
+                if not (lam.dtype == torch.float32 and lam.device == self.dev and lam.numel() == n):
+                    raise ValueError('mix_batch: lam is a float32 tensor of %d factors on %s, or a python float' % (n, self.dev))
+                self.mix_lam[s][:n].copy_(lam.reshape(n), non_blocking=True)
+            else:
+                self.mix_lam[s][:n].fill_(float(lam))
+        if self.in_kind[s] == 'u8':
+            buf, kind = self.in_u8[s], _lib.MIX_U8
+        else:
+            buf, kind = self.in_bufs[s], self.cdtype
+        ctx.call('ifcbk_batch_mix', _vp(buf), kind, n, self.net.S, _vp(self.mix_lam[s]), y0, y1, x0, x1, stream)
         return n
 
     def make_dropout_mask(self, N):

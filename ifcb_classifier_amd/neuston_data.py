@@ -33,8 +33,9 @@ def default_loader(path):
 class RoiTransform:
     """What ``transforms.Compose([flips] + [Resize, ToTensor, Normalize?])`` means on the GPU path."""
 
-    def __init__(self, resize, img_norm=None, vflip=False, hflip=False, rot90=False, pad=None, jitter=None):
+    def __init__(self, resize, img_norm=None, vflip=False, hflip=False, rot90=False, pad=None, jitter=None, mix=None):
         self.resize = resize
+        self.mix = mix                    # --mixup / --cutmix: None, or the BatchMix that draws per batch (the training transform only)
         self.jitter = parse_jitter(jitter)   # --jitter: None, or [B, C] = the brightness / contrast ranges of ColorJitter (not both 0)
         self.pad = parse_pad(pad)         # --pad: None = squash to resize x resize, 'border' / 0..255 = keep the aspect ratio, fill the rest
         self.img_norm = img_norm          # (mean[3], std[3]) or None
@@ -89,6 +90,90 @@ def jitter_arg(text):
         return parse_jitter(text)
     except ValueError:
         raise argparse.ArgumentTypeError('B[,C] must be one or two finite floats >= 0, got %r' % text)
+
+
+def parse_mix_alpha(value, name='mixup'):
+    """``--mixup ALPHA`` / ``--cutmix ALPHA`` / a checkpoint's value: None, a number or its string -> 0.0 (off, also for None and 0) or a
+    finite float > 0, the parameter of the Beta(ALPHA, ALPHA) draw"""
+    if value is None:
+        return 0.0
+    if isinstance(value, bool):
+        raise ValueError('%s: ALPHA expected, got %r' % (name, value))
+    v = float(value)                                                    # (float('a') raises ValueError too)
+    if not 0.0 <= v < float('inf'):                                     # (nan fails both comparisons)
+        raise ValueError('%s: ALPHA must be a finite float >= 0 (0 = off), got %r' % (name, value))
+    return v
+
+
+def parse_mix_prob(value):
+    """``--mix-prob P`` / a checkpoint's ``mix_prob``: None -> 1.0, else a float in [0, 1]"""
+    if value is None:
+        return 1.0
+    if isinstance(value, bool):
+        raise ValueError('mix-prob: P expected, got %r' % (value,))
+    v = float(value)
+    if not 0.0 <= v <= 1.0:                                             # (nan fails both comparisons)
+        raise ValueError('mix-prob: P must be in [0, 1], got %r' % (value,))
+    return v
+
+
+def mix_alpha_arg(text):
+    """argparse ``type=`` of ``--mixup ALPHA`` and ``--cutmix ALPHA`` (neuston_net TRAIN)"""
+    import argparse
+    try:
+        return parse_mix_alpha(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError('ALPHA must be a finite float >= 0 (0 = off), got %r' % text)
+
+
+def mix_prob_arg(text):
+    """argparse ``type=`` of ``--mix-prob P`` (neuston_net TRAIN)"""
+    import argparse
+    try:
+        return parse_mix_prob(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError('P must be a float in [0, 1], got %r' % text)
+
+
+def cut_box(lam0, cy, cx, S):
+    """timm's ``rand_bbox`` with no margin, the centre given: (y0, y1, x0, x1) of the box cut for a Beta draw ``lam0``"""
+    cut_h = cut_w = int(S * np.sqrt(1.0 - lam0))
+    y0, y1 = int(np.clip(cy - cut_h // 2, 0, S)), int(np.clip(cy + cut_h // 2, 0, S))
+    x0, x1 = int(np.clip(cx - cut_w // 2, 0, S)), int(np.clip(cx + cut_w // 2, 0, S))
+    return y0, y1, x0, x1
+
+
+def box_lam(box, S):
+    """timm's ``correct_lam``: the share of the image outside the box"""
+    y0, y1, x0, x1 = box
+    return 1.0 - (y1 - y0) * (x1 - x0) / float(S * S)
+
+
+class BatchMix:
+    """The per-batch draw of TRAIN --mixup / --cutmix, after timm's ``Mixup`` in batch mode: one ``lam`` (and, for CutMix, one box) per
+    batch; the partner of image n is image N - 1 - n.  ``mixup`` / ``cutmix``: the Beta parameters, 0 = off (not both); ``prob``: the
+    probability that a batch is mixed at all.  The draws come from a generator of this object's own, seeded from (seed, rank): neither
+    ``random`` nor the global numpy / torch streams are touched, so a run without the flags keeps its streams bit for bit."""
+
+    def __init__(self, mixup=0.0, cutmix=0.0, prob=1.0, seed=0, rank=0):
+        self.mixup, self.cutmix, self.prob = parse_mix_alpha(mixup, 'mixup'), parse_mix_alpha(cutmix, 'cutmix'), parse_mix_prob(prob)
+        if not (self.mixup > 0 or self.cutmix > 0):
+            raise ValueError('BatchMix: one of mixup and cutmix must be > 0')
+        self.rng = np.random.Generator(np.random.PCG64(np.random.SeedSequence([0x6d6978, int(seed or 0) & 0xffffffffffffffff, int(rank)])))
+
+    def draw(self, S):
+        """-> (lam, box): lam a python float in [0, 1], box None (Mixup, or an unmixed batch: lam == 1) or (y0, y1, x0, x1) (CutMix, with
+        lam corrected to the share of the image outside the box).  Order of the draws: mixed at all (only with prob < 1), which of the
+        two (only with both set: CutMix with probability 0.5, timm's switch_prob), the Beta value, the box centre cy then cx."""
+        if self.prob < 1.0 and not self.rng.random() < self.prob:
+            return 1.0, None
+        cut = self.cutmix > 0 and (not self.mixup > 0 or self.rng.random() < 0.5)
+        if not cut:
+            return float(self.rng.beta(self.mixup, self.mixup)), None
+        lam0 = float(self.rng.beta(self.cutmix, self.cutmix))
+        cy, cx = int(self.rng.integers(0, S)), int(self.rng.integers(0, S))
+        box = cut_box(lam0, cy, cx, S)
+        return box_lam(box, S), box
 
 
 def parse_pad(value):
@@ -359,7 +444,13 @@ def get_trainval_transforms(args):
     rot90 = getattr(args, 'rot90', None)                   # None (unset) | 'T' (training set) | '+V' (validation set as well)
     pad = getattr(args, 'pad', None)                       # geometry, not augmentation: both sets alike
     jitter = getattr(args, 'jitter', None)                 # photometric augmentation: the training set only
-    train = RoiTransform(args.resize, norm, vflip, hflip, rot90=bool(rot90), pad=pad, jitter=jitter)
+    # batch mixing (--mixup / --cutmix): the training set only; absent or 0: no BatchMix object, no draw
+    mixup, cutmix = parse_mix_alpha(getattr(args, 'mixup', None), 'mixup'), parse_mix_alpha(getattr(args, 'cutmix', None), 'cutmix')
+    mix = None
+    if mixup > 0 or cutmix > 0:
+        mix = BatchMix(mixup, cutmix, parse_mix_prob(getattr(args, 'mix_prob', None)), seed=getattr(args, 'seed', 0) or 0,
+                       rank=int(os.environ.get('RANK', 0)))
+    train = RoiTransform(args.resize, norm, vflip, hflip, rot90=bool(rot90), pad=pad, jitter=jitter, mix=mix)
     val = RoiTransform(args.resize, norm, vflip and '+V' in flip, hflip and '+V' in flip, rot90=rot90 == '+V', pad=pad)
     return train, val
 

@@ -289,12 +289,18 @@ class NeustonModel(nn.Module):
         cw = getattr(hparams, 'class_weights', None)
         ls = float(getattr(hparams, 'label_smoothing', None) or 0.0)
         fg = float(getattr(hparams, 'focal_gamma', None) or 0.0)
+        # additive (TRAIN --mixup / --cutmix / --mix-prob): batch mixing with a two-target loss; absent (older files) = off
+        self.mixup = float(getattr(hparams, 'mixup', None) or 0.0)
+        self.cutmix = float(getattr(hparams, 'cutmix', None) or 0.0)
+        mp = getattr(hparams, 'mix_prob', None)
+        self.mix_prob = 1.0 if mp is None else float(mp)
+        self.batch_mix = None             # a neuston_data.BatchMix: fit_batch / fit_batch_ddp then mix every batch they load
         self.model = get_namebrand_model(hparams.MODEL, len(hparams.classes), hparams.pretrained, device, mb,
                                          getattr(hparams, 'precision', 'bf16') or 'bf16', optimizer=opt,
                                          lr=float(getattr(hparams, 'learning_rate', None) or 0.001),
                                          momentum=float(getattr(hparams, 'momentum', None) or 0.0), train_batch=train_batch,
                                          class_weights=cw, weight_decay=float(getattr(hparams, 'weight_decay', None) or 0.0),
-                                         label_smoothing=ls, focal_gamma=fg)
+                                         label_smoothing=ls, focal_gamma=fg, mix=self.mixup > 0 or self.cutmix > 0)
         # what upstream would have written at neuston_models.py:55; the engine's fused loss ops compute the same weighted, smoothed mean
         eng = self.model.engine
         cwt = None if cw is None else eng.class_weight.clone()
@@ -348,6 +354,14 @@ class NeustonModel(nn.Module):
         self.agg_train_loss += batch_loss.item()
         return dict(loss=batch_loss)
 
+    def _mix_loaded(self, mix, n, slot=None):
+        """TRAIN --mixup / --cutmix: draw this batch's (lam, box) from ``mix`` (a neuston_data.BatchMix) and mix the n images just loaded
+        into the slot (``slot`` None: the current one); the train loss ops read the factors from the engine.  Needs an engine built with
+        mixing (hparams ``mixup`` / ``cutmix``): ``Engine.mix_batch`` raises otherwise."""
+        eng = self.model.engine
+        lam, box = mix.draw(eng.net.S)
+        eng.mix_batch(n, lam, box, slot=slot)
+
     # TRAINING (fast path: one fused HIP program; loss accumulated on device, read once per epoch) #
     def fit_batch(self, input_data, input_classes):
         eng = self.model.engine
@@ -356,6 +370,8 @@ class NeustonModel(nn.Module):
         else:
             N = eng.load_rois(**input_data)
         eng.target[:N].copy_(input_classes, non_blocking=True)
+        if self.batch_mix is not None:
+            self._mix_loaded(self.batch_mix, N)
         self.model.train()
         eng.train_step(N)
         return N
@@ -374,6 +390,8 @@ class NeustonModel(nn.Module):
             n = eng.load_rois(slot=slot, **kw)
             if input_classes is not None:
                 eng.tgt_bufs[slot][:n].copy_(input_classes, non_blocking=True)
+                if getattr(transform, 'mix', None) is not None:
+                    self._mix_loaded(transform.mix, n, slot=slot)       # (the training transform only carries one)
         eng.prefetch_end(slot)
         return n
 
@@ -440,6 +458,8 @@ class NeustonModel(nn.Module):
         eng = self.model.engine
         N = eng.load_input_nchw(input_data) if torch.is_tensor(input_data) else eng.load_rois(**input_data)
         eng.target[:N].copy_(input_classes, non_blocking=True)
+        if self.batch_mix is not None:
+            self._mix_loaded(self.batch_mix, N)
         self.model.train()
         eng.train_step_ddp(N, world, all_reduce)
         return N

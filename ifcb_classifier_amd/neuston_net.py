@@ -21,7 +21,7 @@ from torch.utils.data import DataLoader
 
 from .neuston_callbacks import SaveValidationResults, SaveTestResults
 from .neuston_data import (get_trainval_datasets, IfcbBinDataset, ImageDataset, IMG_EXTENSIONS, collate_rois,
-                           jitter_arg, pad_arg, rois_to_device)
+                           jitter_arg, mix_alpha_arg, mix_prob_arg, pad_arg, rois_to_device)
 from .neuston_models import NeustonModel, load_checkpoint_file, load_pretrained_weights
 
 
@@ -83,6 +83,11 @@ class _ExclusiveLossScalar(argparse.Action):
         setattr(namespace, self.dest, value)
         if all(getattr(namespace, d, 0.0) for d in self.FLAGS):
             parser.error('%s and %s do not combine: give one of them' % tuple(sorted(self.FLAGS.values(), reverse=True)))
+        # batch mixing (--mixup / --cutmix) has a two-target loss of its own, which has no focal form
+        if getattr(namespace, 'focal_gamma', 0.0):
+            for d, flag in (('mixup', '--mixup'), ('cutmix', '--cutmix')):
+                if getattr(namespace, d, 0.0):
+                    parser.error('%s and --focal-gamma do not combine: give one of them' % flag)
 
 
 def _dist():
@@ -579,6 +584,9 @@ def argparse_nn_train(train_subparser):
     augs.add_argument('--flip', choices=['x', 'y', 'xy', 'x+V', 'y+V', 'xy+V'], help='Training images have 50%% chance of being flipped along the designated axis: (x) vertically, (y) horizontally, (xy) either/both. "+V" includes the Validation dataset')
     augs.add_argument('--rot90', nargs='?', const='T', choices=['T', '+V'], default=None, help='(MI355X path, additive) Training images are rotated counter-clockwise by k quarter turns, k uniform in {0,1,2,3}, after any --flip and before the resize. "+V" includes the Validation dataset. With "--flip xy" the eight symmetries of the square are equally likely. Default (unset) is no rotation')
     augs.add_argument('--jitter', metavar='B[,C]', type=jitter_arg, default=None, help='(MI355X path, additive) Brightness / contrast jitter of the training images, as transforms.ColorJitter(brightness=B, contrast=C) in front of the resize: per image a brightness factor uniform in [max(0, 1-B), 1+B] and a contrast factor uniform in [max(0, 1-C), 1+C] (PIL.ImageEnhance arithmetic, on the GPU; always brightness first). B and C are finite floats >= 0, C defaults to 0. Training set only. Default (unset, also "0") is no jitter')
+    augs.add_argument('--mixup', metavar='ALPHA', type=mix_alpha_arg, default=0.0, action=_ExclusiveLossScalar, help='(MI355X path, additive) Mixup of the training batches, as timm\'s Mixup in batch mode: per batch lam ~ Beta(ALPHA, ALPHA), every image becomes lam * image + (1 - lam) * partner, the partner being the image at the mirrored place of the batch, and the loss takes both labels with weights lam and 1 - lam. Mixed on the GPU after the resize. A finite float > 0; composes with --class-norm and --label-smoothing, not with --focal-gamma; val_loss stays unmixed. Default is 0 (off)')
+    augs.add_argument('--cutmix', metavar='ALPHA', type=mix_alpha_arg, default=0.0, action=_ExclusiveLossScalar, help='(MI355X path, additive) CutMix of the training batches, as timm\'s Mixup(cutmix_alpha=ALPHA) in batch mode: per batch a box covering about 1 - Beta(ALPHA, ALPHA) of the image is filled from the partner image, and lam is the share left outside the box. With --mixup as well, each batch is CutMix with probability 0.5, else Mixup. A finite float > 0; not with --focal-gamma. Default is 0 (off)')
+    augs.add_argument('--mix-prob', metavar='P', type=mix_prob_arg, default=1.0, help='(MI355X path, additive) Probability that a training batch is mixed at all by --mixup / --cutmix. A float in [0, 1]. Default is 1')
     out = t.add_argument_group(title='Output Options')
     out.add_argument('--outdir', default='training-output/{TRAIN_ID}', help='Default is "training-output/{TRAIN_ID}"')
     out.add_argument('--model-id', default='{TRAIN_ID}', help='Set a specific model id. Patterns {TRAIN_DATE} and {TRAIN_ID} are recognized. Default is "{TRAIN_ID}"')

@@ -249,6 +249,18 @@ IFCBK_API int ifcbk_softmax_xent_ls(ifcbk_ctx*, const float* logits, const int64
 IFCBK_API int ifcbk_softmax_xent_focal(ifcbk_ctx*, const float* logits, const int64_t* target, const float* class_weight /*nullable*/, int N,
                           int NC, float weight, float gamma, float* loss_out, int loss_accumulate, float* dlogits /*nullable*/,
                           void* stream);
+/* the two-target loss of a mixed batch (TRAIN --mixup / --cutmix; ifcbk_batch_mix pairs image i with N - 1 - i) on the same operands.
+ * a = target[i], b = target[N - 1 - i], lam_i = lam[i] in [0, 1], p = softmax(logits), w = class_weight (NULL = all ones),
+ * c1 = 1 - eps, eC = eps / NC, SW = sum_k w[k], h_i = lam_i w[a] + (1 - lam_i) w[b], W = sum_i h_i:
+ * loss_out[0] (+)= weight / W * sum_i [ c1 (lam_i w[a] (-log p_i[a]) + (1 - lam_i) w[b] (-log p_i[b])) + eC sum_j w[j] (-log p_i[j]) ];
+ * dlogits_i[j] = weight / W * [ (c1 h_i + eC SW) p_i[j] - c1 lam_i w[a] [j == a] - c1 (1 - lam_i) w[b] [j == b] - eC w[j] ].
+ * Without weights W = N: timm's SoftTargetCrossEntropy on mixup_target.  lam == 1 everywhere is ifcbk_softmax_xent_ls's function (not
+ * its bits); a == b is legal.  IFCBK_EINVAL: lam NULL, label_smoothing outside [0, 1] or not finite, N or NC < 1, NULL logits / target /
+ * loss_out; a lam outside [0, 1] is the caller's fault, as a target outside [0, NC) is.  One block, fixed summation order: bitwise
+ * reproducible.                                                                                                                      */
+IFCBK_API int ifcbk_softmax_xent_mix(ifcbk_ctx*, const float* logits, const int64_t* target, const float* lam /*[N]*/,
+                           const float* class_weight /*nullable*/, int N, int NC, float weight, float label_smoothing, float* loss_out,
+                           int loss_accumulate, float* dlogits /*nullable*/, void* stream);
 /* the bookkeeping of one fused train step, in the step's own op table (no framework kernel between the first and the last
  * launch of a step): num_batches_tracked[0..n) += 1 of every BatchNorm ([PL]/torch: nn.BatchNorm2d.forward in training) and
  * loss_sum += loss (the reference's train_loss is the SUM of the batch losses, neuston_models.py:85).  Either part may be NULL. */
@@ -311,6 +323,17 @@ IFCBK_API int ifcbk_roi_jitter(ifcbk_ctx*, const uint8_t* pixels, const int64_t*
                          int n_img, int in_channels /*1|3*/, int max_h, int max_w,
                          const float* brightness /*[n_img], nullable*/, const float* contrast /*[n_img], nullable*/,
                          uint8_t* out /* same layout as pixels; may be == pixels */, void* stream);
+/* mix a RESIZED batch with its reverse, in place (TRAIN --mixup / --cutmix; timm's Mixup in batch mode: the partner of image n is
+ * m = N - 1 - n).  x is the u8 plane [N][S][S] a grey batch is resized to (kind = IFCBK_MIX_U8; any address) or the dense tensor
+ * [N][S][S][8] (kind = IFCBK_BF16 / IFCBK_F32; 16-byte aligned).  Inside the box [y0, y1) x [x0, x1) the partners' pixels are swapped
+ * (exact copies); outside it x'[n] = fmaf(lam[n], x[n] - x[m], x[m]) in fp32 -- each row with its own factor -- stored as
+ * (uint8_t)(int)(v + 0.5f), round-to-nearest-even bf16, or fp32; a row with lam == 1 keeps its bytes.  An empty box (y0 == y1 or
+ * x0 == x1) cuts nothing.  The middle image of an odd N is left alone and N == 1 launches nothing.  No byte outside the N images is
+ * read or written.  IFCBK_EINVAL: x or lam NULL, N < 1, S < 1 (or > 32768), a box outside [0, S], y0 > y1, x0 > x1, an unknown kind,
+ * a dense tensor that is not 16-byte aligned. */
+#define IFCBK_MIX_U8 2
+IFCBK_API int ifcbk_batch_mix(ifcbk_ctx*, void* x, int kind /* IFCBK_MIX_U8 | IFCBK_BF16 | IFCBK_F32 */, int N, int S,
+                         const float* lam /*[N], device*/, int y0, int y1, int x0, int x1, void* stream);
 /* per-image, per-channel integer moments of a u8 plane [n_img][pixels_per_img][channels] (channels 1..4):
    out[i][c][0] = sum of v, out[i][c][1] = sum of v*v, exact (uint64); n_img = 0 is a no-op.
  * x is typically out_u8 of ifcbk_roi_preprocess; mean = sum v / (255 n), population std from the two sums.
@@ -439,7 +462,10 @@ enum {
                               * (nullable); i: N, NC; f[0] = weight): 0, what a zeroed op holds, is the unsmoothed call; any other value
                               * runs ifcbk_softmax_xent_ls with the same operands (class_weight = p[4] here, NULL for the plain kind).
                               * f[2] = focal-loss gamma, for the same two kinds: 0 is today's call; any other value runs
-                              * ifcbk_softmax_xent_focal with the same operands; f[1] != 0 together with f[2] != 0 is IFCBK_EINVAL      */
+                              * ifcbk_softmax_xent_focal with the same operands; f[1] != 0 together with f[2] != 0 is IFCBK_EINVAL.
+                              * p[5] = the factors of a mixed batch (float[N], device), for the same two kinds: NULL, what a zeroed op
+                              * holds, is the dispatch above; an array runs ifcbk_softmax_xent_mix with the same operands and f[1] as its
+                              * label smoothing; an array together with f[2] != 0 is IFCBK_EINVAL                                       */
 };
 typedef struct {
     ifcbk_conv_desc d;
