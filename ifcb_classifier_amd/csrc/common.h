@@ -28,6 +28,7 @@ struct ifcbk_ctx {
     hipEvent_t* slot_ev[256];   // ifcbk_run_program_ev: (start, stop) per op
     int slot_n[256];
     unsigned char* slot_rec[256];   // which ops of the slot's last run were bracketed (flags bit 7)
+    int slot_ops[256];              // op count of the slot's last run; ifcbk_program_times refuses more (never ran: slot_rec is null)
     char err[512];
 };
 

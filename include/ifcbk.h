@@ -495,7 +495,8 @@ IFCBK_API int ifcbk_run_program(ifcbk_ctx*, const ifcbk_op* ops, int n, void* st
 /* Non-blocking timing: same launches, with HIP events recorded (on the op's lane) around every op whose flags
  * have bit 7 set, into event slot `slot` (0..255, one slot per in-flight program run); nothing is synchronised.  After the caller has
  * synchronised the stream, ifcbk_program_times returns the n per-op milliseconds of that slot (0 for ops
- * that were not bracketed).                                                                              */
+ * that were not bracketed).  n is at most the op count of the slot's last run: a larger n, or a slot that never ran, is
+ * IFCBK_EINVAL (events behind that count belong to an earlier, longer run).                             */
 IFCBK_API int ifcbk_run_program_ev(ifcbk_ctx*, const ifcbk_op* ops, int n, void* stream, int slot);
 IFCBK_API int ifcbk_program_times(ifcbk_ctx*, int slot, int n, float* op_ms);
 /* hipGraph replay of a program (BASELINE config 4: "hipGraph-captured batches").  ifcbk_program_capture records the
@@ -506,7 +507,10 @@ IFCBK_API int ifcbk_program_times(ifcbk_ctx*, int slot, int n, float* op_ms);
  * The per-lane workspace arenas are baked in as well: ifcbk_ctx_reserve growing the workspace invalidates every graph
  * of the ctx (ifcbk_graph_launch then fails with IFCBK_EINVAL instead of replaying stale pointers).  Lifetime: a graph belongs
  * to the ctx it was captured through -- launch / destroy it through that ctx only (anything else is IFCBK_EINVAL), and
- * ifcbk_ctx_destroy destroys the graphs the caller left, BEFORE the arenas / streams / events they were built from.             */
+ * ifcbk_ctx_destroy destroys the graphs the caller left, BEFORE the arenas / streams / events they were built from.
+ * Not captured: a program that holds an IFCBK_OP_MEMSET is refused with IFCBK_EUNSUPPORTED before anything is recorded.  A graph of
+ * memset nodes replayed wrong bytes on a later launch (a one-stream capture of four 4 KiB memsets, no error from the runtime; cause
+ * not known), where graphs of kernel nodes replay right; no plan of the engine emits the kind.  ifcbk_run_program runs it.          */
 typedef struct ifcbk_graph ifcbk_graph;
 IFCBK_API int ifcbk_program_capture(ifcbk_ctx*, const ifcbk_op* ops, int n, ifcbk_graph** out);
 IFCBK_API int ifcbk_graph_launch(ifcbk_ctx*, ifcbk_graph*, void* stream);

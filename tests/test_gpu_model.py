@@ -353,15 +353,16 @@ def test_a_graph_belongs_to_its_ctx_and_dies_with_it():
     assert eng.ctx.h is None and not eng.plan_graph_handles()
     # (c) without the engine's help: the ctx destroys what the caller left
     ctx2 = _lib.Context(0)
-    ops = (_lib.Op * 1)()
-    ops[0].kind = _lib.OP_MEMSET
-    buf = torch.zeros(64, device='cuda')
-    ops[0].p[0] = buf.data_ptr()
-    ops[0].i[0], ops[0].i[1] = 64, 0
+    ops = (_lib.Op * 1)()                                                                 # (a kernel node: a memset is not captured, ifcbk.h)
+    ops[0].kind = _lib.OP_SOFTMAX
+    buf, out = torch.zeros(8, 8, device='cuda'), torch.zeros(8, 8, device='cuda')
+    ops[0].p[0], ops[0].p[1] = buf.data_ptr(), out.data_ptr()
+    ops[0].i[0], ops[0].i[1] = 8, 8
     g2 = ctx2.capture(ops, 1)
     assert ctx2.live_graphs() == 1
     ctx2.graph_launch(g2, _lib.cur_stream())
     torch.cuda.synchronize()
+    assert torch.equal(out, torch.full_like(out, 0.125))
     assert lib.ifcbk_graph_destroy(ctx2.h, g2) == 0 and ctx2.live_graphs() == 0
     g3 = ctx2.capture(ops, 1)
     assert ctx2.live_graphs() == 1 and g3

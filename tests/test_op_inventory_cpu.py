@@ -18,8 +18,6 @@ EXEMPT_API = {
     'ifcbk_ctx_set_lanes': 'called by Engine.__init__, so by every whole-model test; test_lanes_cpu.py checks the lane plan itself',
     'ifcbk_ctx_live_graphs': 'reached through Context.live_graphs (test_gpu_model.py)',
     'ifcbk_run_program': 'reached through Context.run_program (test_gpu_conv_forced.py, every Engine step)',
-    'ifcbk_run_program_ev': 'the event-timed variant of the same runner (the engine\'s per-op timing mode); same launches as ifcbk_run_program',
-    'ifcbk_program_times': 'host read-back of the events of ifcbk_run_program_ev; launches nothing',
     'ifcbk_program_capture': 'reached through Context.capture (test_gpu_model.py)',
     'ifcbk_op_cost': 'host-only bookkeeping (flops / bytes of an op) used by the profiling scripts; launches nothing',
 }
