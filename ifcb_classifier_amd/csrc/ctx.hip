@@ -131,6 +131,10 @@ extern "C" int ifcbk_ctx_live_graphs(ifcbk_ctx* c) { return c ? c->n_graphs : 0;
 
 extern "C" const char* ifcbk_last_error(ifcbk_ctx* c) { return c ? c->err : g_create_err; }
 
+// the weight average's slice of an optimizer op (TRAIN --ema): the operand behind those of the plain step, p[4] of IFCBK_OP_ADAM (its
+// weight: f[6]) and p[3] of IFCBK_OP_SGD (f[4]); NULL, what a zeroed op holds, is the step without an average
+static float* op_ema(const ifcbk_op* o) { return (float*)o->p[o->kind == IFCBK_OP_ADAM ? 4 : 3]; }
+
 static int run_one(ifcbk_ctx* c, const ifcbk_op* o, void* st) {
     void* const* p = o->p;
     const int acc = o->flags & 1, pacc = (o->flags >> 1) & 1;
@@ -232,10 +236,11 @@ static int run_one(ifcbk_ctx* c, const ifcbk_op* o, void* st) {
                                         (float*)p[2], acc, (float*)p[3], st);
         case IFCBK_OP_SOFTMAX: return ifcbk_softmax(c, (const float*)p[0], (int)o->i[0], (int)o->i[1], (float*)p[1], st);
         case IFCBK_OP_ADAM:
-            return ifcbk_adam_flat(c, (float*)p[0], (const float*)p[1], (float*)p[2], (float*)p[3], o->i[0], o->f[0], o->f[1],
-                                   o->f[2], o->f[3], o->f[4], (int)o->i[1], o->f[5], st);
+            return ifcbk_adam_ema_flat(c, (float*)p[0], (const float*)p[1], (float*)p[2], (float*)p[3], op_ema(o), o->i[0], o->f[0],
+                                       o->f[1], o->f[2], o->f[3], o->f[4], (int)o->i[1], o->f[5], o->f[6], st);
         case IFCBK_OP_SGD:
-            return ifcbk_sgd_flat(c, (float*)p[0], (const float*)p[1], (float*)p[2], o->i[0], o->f[0], o->f[1], o->f[2], o->f[3], st);
+            return ifcbk_sgd_ema_flat(c, (float*)p[0], (const float*)p[1], (float*)p[2], op_ema(o), o->i[0], o->f[0], o->f[1], o->f[2],
+                                      o->f[3], o->f[4], st);
         case IFCBK_OP_MEMSET:
             IFCBK_HIP(c, hipMemsetAsync(p[0], (int)o->i[1], (size_t)o->i[0], (hipStream_t)st));
             return 0;
@@ -728,8 +733,8 @@ extern "C" int ifcbk_op_cost(const ifcbk_op* o, double* flops, double* bytes) {
             by = (double)d.N * d.HW * d.C * 2;
             break;
         }
-        case IFCBK_OP_ADAM: by = (double)o->i[0] * 28; break;
-        case IFCBK_OP_SGD: by = (double)o->i[0] * (o->p[2] ? 20 : 12); break;
+        case IFCBK_OP_ADAM: by = (double)o->i[0] * (28 + (o->p[4] ? 8 : 0)); break;      // (+ the weight average: read and written)
+        case IFCBK_OP_SGD: by = (double)o->i[0] * ((o->p[2] ? 20 : 12) + (o->p[3] ? 8 : 0)); break;
         case IFCBK_OP_SOFTMAX_XENT: case IFCBK_OP_SOFTMAX_XENT_W:
             if (o->p[5]) {                  // the two-target loss: logits in, dlogits out (when asked for), targets and factors
                 fl = (double)o->i[0] * o->i[1] * 12;

@@ -610,7 +610,8 @@ __global__ void softmax_kernel(const float* logits, int N, int NC, float* probs)
 // ---------------------------------------------------------------- optimizers (flat)
 __global__ __launch_bounds__(256) void adam_kernel(float* p, const float* g, float* m, float* v, int64_t n, float lr,
                                                    float b1, float b2, float eps, float wd, float bc1, float sbc2,
-                                                   float gscale) {
+                                                   float gscale, float* ema, float ew) {
+    // ema (nullable, wave-uniform): the weight average e += ew * (p - e) of the p this step writes, taken from the registers
     int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
     if (i >= n) return;
     if (i + 4 <= n) {
@@ -628,18 +629,27 @@ __global__ __launch_bounds__(256) void adam_kernel(float* p, const float* g, flo
         *reinterpret_cast<float4*>(p + i) = pp;
         *reinterpret_cast<float4*>(m + i) = mm;
         *reinterpret_cast<float4*>(v + i) = vv;
+        if (ema) {
+            float4 ee = *reinterpret_cast<float4*>(ema + i);
+            float* E = &ee.x;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) E[j] = E[j] + ew * (P[j] - E[j]);
+            *reinterpret_cast<float4*>(ema + i) = ee;
+        }
     } else {
         for (int64_t k = i; k < n; ++k) {
             float gr = g[k] * gscale + wd * p[k];
             m[k] = b1 * m[k] + (1.f - b1) * gr;
             v[k] = b2 * v[k] + (1.f - b2) * gr * gr;
             float denom = sqrtf(v[k]) / sbc2 + eps;
-            p[k] -= (lr / bc1) * (m[k] / denom);
+            float pn = p[k] - (lr / bc1) * (m[k] / denom);
+            p[k] = pn;
+            if (ema) ema[k] = ema[k] + ew * (pn - ema[k]);
         }
     }
 }
 __global__ __launch_bounds__(256) void sgd_kernel(float* p, const float* g, float* mom, int64_t n, float lr, float mu,
-                                                  float wd, float gscale) {
+                                                  float wd, float gscale, float* ema, float ew) {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     float gr = g[i] * gscale + wd * p[i];
@@ -648,7 +658,9 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* p, const float* g, floa
         mom[i] = b;
         gr = b;
     }
-    p[i] -= lr * gr;
+    float pn = p[i] - lr * gr;
+    p[i] = pn;
+    if (ema) ema[i] = ema[i] + ew * (pn - ema[i]);          // (as adam_kernel: the weight average of the p just written)
 }
 
 // ---------------------------------------------------------------- layout
@@ -840,20 +852,36 @@ extern "C" int ifcbk_softmax(ifcbk_ctx* ctx, const float* logits, int N, int NC,
     return 0;
 }
 
-extern "C" int ifcbk_adam_flat(ifcbk_ctx* ctx, float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1,
-                               float beta2, float eps, float weight_decay, int step, float grad_scale, void* stream) {
+// the weight of a fused weight average: [0, 1] (a NaN fails both comparisons); 0 is "no update", which the callers launch as ema = NULL
+static bool ema_w_ok(float w) { return w >= 0.f && w <= 1.f; }
+extern "C" int ifcbk_adam_ema_flat(ifcbk_ctx* ctx, float* p, const float* g, float* m, float* v, float* ema, int64_t n, float lr,
+                                   float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale, float ema_w,
+                                   void* stream) {
     if (step < 1) IFCBK_FAIL(ctx, IFCBK_EINVAL, "adam: step must be >= 1");
+    if (ema && !ema_w_ok(ema_w)) IFCBK_FAIL(ctx, IFCBK_EINVAL, "adam: ema_w %g outside [0, 1]", (double)ema_w);
+    if (ema && ((uintptr_t)ema & 15) != ((uintptr_t)p & 15)) IFCBK_FAIL(ctx, IFCBK_EINVAL, "adam: ema must be aligned as p is");
+    if (ema_w == 0.f) ema = nullptr;
     float bc1 = 1.f - powf(beta1, (float)step);
     float sbc2 = sqrtf(1.f - powf(beta2, (float)step));
-    hipLaunchKernelGGL(adam_kernel, dim3(cdiv(cdiv(n, 4), 256)), dim3(256), 0, ST, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, sbc2, grad_scale);
+    hipLaunchKernelGGL(adam_kernel, dim3(cdiv(cdiv(n, 4), 256)), dim3(256), 0, ST, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, sbc2, grad_scale, ema, ema_w);
     IFCBK_LAUNCH_CHECK(ctx, "adam");
+    return 0;
+}
+extern "C" int ifcbk_adam_flat(ifcbk_ctx* ctx, float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1,
+                               float beta2, float eps, float weight_decay, int step, float grad_scale, void* stream) {
+    return ifcbk_adam_ema_flat(ctx, p, g, m, v, nullptr, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, 0.f, stream);
+}
+extern "C" int ifcbk_sgd_ema_flat(ifcbk_ctx* ctx, float* p, const float* g, float* mom, float* ema, int64_t n, float lr, float momentum,
+                                  float weight_decay, float grad_scale, float ema_w, void* stream) {
+    if (ema && !ema_w_ok(ema_w)) IFCBK_FAIL(ctx, IFCBK_EINVAL, "sgd: ema_w %g outside [0, 1]", (double)ema_w);
+    if (ema_w == 0.f) ema = nullptr;
+    hipLaunchKernelGGL(sgd_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ST, p, g, mom, n, lr, momentum, weight_decay, grad_scale, ema, ema_w);
+    IFCBK_LAUNCH_CHECK(ctx, "sgd");
     return 0;
 }
 extern "C" int ifcbk_sgd_flat(ifcbk_ctx* ctx, float* p, const float* g, float* mom, int64_t n, float lr, float momentum,
                               float weight_decay, float grad_scale, void* stream) {
-    hipLaunchKernelGGL(sgd_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ST, p, g, mom, n, lr, momentum, weight_decay, grad_scale);
-    IFCBK_LAUNCH_CHECK(ctx, "sgd");
-    return 0;
+    return ifcbk_sgd_ema_flat(ctx, p, g, mom, nullptr, n, lr, momentum, weight_decay, grad_scale, 0.f, stream);
 }
 
 extern "C" int ifcbk_nchw_to_nhwc(ifcbk_ctx* ctx, const float* x, int N, int C, int H, int W, int Cpad, int dtype,

@@ -5,6 +5,7 @@ No autograd, no tracing: the graph is static (``graph.py``), so forward, backwar
 pre-built op tables; one FFI crossing launches a whole step.  PyTorch is used only for device memory and
 streams.  The HIP library is mandatory -- there is no CPU fallback in this module.
 """
+import contextlib
 import ctypes as C
 import math
 import os
@@ -33,6 +34,18 @@ def dtype_is_bf16(eng):
 
 def _vp(t, byte_off=0):
     return None if t is None else C.c_void_p(t.data_ptr() + byte_off)
+
+
+def ema_decay_at(decay, t, warmup=True):
+    """decay of the t-th update (t = 1, 2, ...) of a weight average since it was initialised: min(decay, (1 + t) / (10 + t)), the
+    warm-up of TensorFlow's ExponentialMovingAverage(num_updates) -- a short training is not held to its initial weights for
+    1 / (1 - decay) steps; warmup=False: decay itself"""
+    return min(float(decay), (1.0 + t) / (10.0 + t)) if warmup else float(decay)
+
+
+def ema_weight(decay, t, warmup=True):
+    """the w of e <- e + w (p - e) for that update: 1 - d_t in double, rounded ONCE to fp32 (what the kernels are given)"""
+    return C.c_float(1.0 - ema_decay_at(decay, t, warmup)).value
 
 
 class OpList:
@@ -181,7 +194,7 @@ class Engine:
 
     def __init__(self, net, device=0, max_batch=32, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, dtype='bf16', optimizer='adam',
                  momentum=0.0, plan_only=False, train_batch=None, dp_world=None, class_weights=None, weight_decay=0.0,
-                 label_smoothing=0.0, focal_gamma=0.0, mix=False):
+                 label_smoothing=0.0, focal_gamma=0.0, mix=False, ema_decay=None, ema_warmup=True):
         # dp_world: world size of the data-parallel job this replica belongs to (None: WORLD_SIZE of the launcher, else an
         # initialised torch.distributed group, else 1) -- it picks the program-lane default, and train_step_ddp checks it
         self._dp_world_arg = None if dp_world is None else int(dp_world)
@@ -220,6 +233,17 @@ class Engine:
         self.mix = bool(mix)
         if self.mix and self.focal_gamma > 0:
             raise ValueError('mix and focal_gamma do not combine: give one of them')
+        # additive (TRAIN --ema): an exponential moving average E / ERB of the parameters P and the BatchNorm running statistics RB, taken
+        # inside the optimizer ops (their p[4] / p[3]) and by one ifcbk_ema_flat call per step; ema_weights() evaluates and exports it.
+        # None: no shadow buffers, and plans, op tables and launches are what they were
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        if self.ema_decay is not None and not 0.0 < self.ema_decay < 1.0:      # (a NaN fails both comparisons)
+            raise ValueError('ema_decay must be in (0, 1), or None for no weight average')
+        self.ema_warmup = bool(ema_warmup)
+        self.ema_stale = True             # P was set from outside the optimizer (params_changed): the next train step starts E = P, ERB = RB
+        self.ema_updates = 0              # t of the decay schedule: updates since E was last initialised
+        self._ema_w = 0.0
+        self._ema_view = None             # (P, RB, stale flag) saved by ema_weights() while the averaged model stands in P / RB
         self.net = net
         if dtype not in ('bf16', 'fp32'):
             raise ValueError("dtype must be 'bf16' (performance) or 'fp32' (parity mode)")
@@ -292,6 +316,7 @@ class Engine:
         self.G = torch.zeros(off, dtype=torch.float32, device=dev)
         self.M = torch.zeros(off, dtype=torch.float32, device=dev)
         self.V = torch.zeros(off, dtype=torch.float32, device=dev)
+        self.E = torch.zeros(off, dtype=torch.float32, device=dev) if self.ema_decay is not None else None      # layout of P
         self.pviews, self.gviews = {}, {}
         for key, (o, n, shape, kind, node) in self.poff.items():
             if kind == 'conv':
@@ -308,6 +333,7 @@ class Engine:
             self.boff[key] = (boff, shape[0])
             boff += shape[0]
         self.RB = torch.zeros(boff, dtype=torch.float32, device=dev)
+        self.ERB = torch.zeros(boff, dtype=torch.float32, device=dev) if self.ema_decay is not None else None   # layout of RB
         self.bviews = {k: self.RB[o:o + n] for k, (o, n) in self.boff.items()}
         for k, v in self.bviews.items():
             if k.endswith('running_var'):
@@ -484,6 +510,59 @@ class Engine:
     def params_changed(self):
         self.packed = False
         self.eval_stats_ready = False
+        self.ema_stale = True             # (the optimizer paths do not come through here: only writes from outside restart the average)
+
+    # ------------------------------------------------------------------ weight average (TRAIN --ema)
+    def _ema_begin_step(self, update=True):
+        """at the start of a train step (update=False: of a training forward that an adam_step will follow): initialise the average if P
+        was set from outside since the last step -- E = P, ERB = RB as they stand BEFORE this step's forward, whichever way the step is
+        launched -- then count the update and round its weight once"""
+        if self.ema_decay is None:
+            return
+        if self._ema_view is not None:
+            raise RuntimeError('a train step inside ema_weights(): P holds the averaged weights there')
+        if self.ema_stale:
+            self.E.copy_(self.P)
+            self.ERB.copy_(self.RB)
+            self.ema_updates = 0
+            self.ema_stale = False
+        if update:
+            self.ema_updates += 1
+            self._ema_w = ema_weight(self.ema_decay, self.ema_updates, self.ema_warmup)
+
+    def _ema_end_step(self):
+        """behind the step program, on its stream: the running statistics are final, ERB takes the update E took inside the optimizer ops"""
+        if self.ema_decay is not None and self.RB.numel():
+            self.ctx.call('ifcbk_ema_flat', _vp(self.ERB), _vp(self.RB), self.RB.numel(), self._ema_w, self.stream())
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """inside: forward_eval, the eval loss and every view of P / RB (the module's state_dict) see the averaged model E / ERB;
+        num_batches_tracked stays the live count.  On leaving, P and RB hold their own bits again (M, V and the step count were never
+        touched) and the next train step repacks from P.  Once per epoch: plain copies, no kernel of its own."""
+        if self.ema_decay is None:
+            raise RuntimeError('ema_weights: this engine was built without ema_decay')
+        if self._ema_view is not None:
+            raise RuntimeError('ema_weights: already inside')
+        if self.ema_stale:
+            # nothing was averaged since P was last set: the average of that model is the model
+            self.E.copy_(self.P)
+            self.ERB.copy_(self.RB)
+            self.ema_updates = 0
+            self.ema_stale = False
+        self._ema_view = (self.P.clone(), self.RB.clone())
+        self.P.copy_(self.E)
+        self.RB.copy_(self.ERB)
+        self.packed = self.eval_stats_ready = False
+        try:
+            yield self
+        finally:
+            p, rb = self._ema_view
+            self.P.copy_(p)
+            self.RB.copy_(rb)
+            self._ema_view = None
+            self.packed = self.eval_stats_ready = False
+            self.ema_stale = False        # (an eval forward of the module inside calls params_changed(): nothing was written)
 
     # ------------------------------------------------------------------ activations
     def _alloc_acts(self):
@@ -1449,12 +1528,15 @@ class Engine:
         sm.add(_lib.OP_SOFTMAX, 'softmax', p=(_vp(main.logits), _vp(self.probs)), i=(N, net.NC))
         pl.softmax = Program(sm)
         opt = OpList()
+        # the weight average (TRAIN --ema) is one more operand of the optimizer op, behind those of the plain step: E at the offset of P
+        # (every bucket's op below carries its slice); its weight is stamped per step (_set_update).  Without it the tuples are what they were
+        ema = (_vp(self.E),) if self.ema_decay is not None else ()
         if self.optimizer == 'sgd':
             # additive option (north_star "SGD/Adam step"; upstream only has Adam): torch.optim.SGD's update, momentum buffer = M
-            opt.add(_lib.OP_SGD, 'sgd', p=(_vp(self.P), _vp(self.G), _vp(self.M) if self.momentum else None),
+            opt.add(_lib.OP_SGD, 'sgd', p=(_vp(self.P), _vp(self.G), _vp(self.M) if self.momentum else None) + ema,
                     i=(self.nparam_padded, 1), f=(self.lr, self.momentum, self.weight_decay, 1.0))
         else:
-            opt.add(_lib.OP_ADAM, 'adam', p=(_vp(self.P), _vp(self.G), _vp(self.M), _vp(self.V)),
+            opt.add(_lib.OP_ADAM, 'adam', p=(_vp(self.P), _vp(self.G), _vp(self.M), _vp(self.V)) + ema,
                     i=(self.nparam_padded, 1), f=(self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, 1.0))
         pl.adam = Program(opt)
         # the step's bookkeeping in the step's own op table: num_batches_tracked += 1 of every BatchNorm, loss_sum += loss
@@ -1533,6 +1615,8 @@ class Engine:
                 for off in own:
                     last_reader[off] = k
         LW = self.NL - 1 if self.wgrad_lane else 0
+        # pointer operands of the optimizer op: P, G, M (, V) and, with a weight average, its slice of E behind them
+        nptr = (4 if self.optimizer != 'sgd' else 3) + (1 if self.ema_decay is not None else 0)
         inserts = {}                           # op index -> OpList to emit BEFORE that op (i.e. behind op index - 1)
         prev_ins = 0
         for (b0, b1, lo, hi) in segs[:-1]:
@@ -1540,9 +1624,9 @@ class Engine:
             prev_ins = ins
             ol = inserts.setdefault(ins, OpList())
             o0 = opt.ops[0]
-            ptrs = [(o0.p[j] + 4 * lo) if o0.p[j] else None for j in range(4 if self.optimizer != 'sgd' else 3)]
+            ptrs = [(o0.p[j] + 4 * lo) if o0.p[j] else None for j in range(nptr)]
             ol.add(o0.kind, opt.tags[0] + '[%d:%d]' % (lo, hi), p=ptrs, i=(hi - lo, int(o0.i[1])), f=tuple(o0.f[j] for j in range(8)),
-                   lane=LW, reads=[('G', lo, hi)], writes=[('P', lo, hi)])
+                   lane=LW, reads=[('G', lo, hi)], writes=[('P', lo, hi)] + ([('E', lo, hi)] if self.ema_decay is not None else []))
             sub = OpList()
             for o, tg, mt in zip(pack_ops.ops, pack_ops.tags, pack_ops.meta):
                 if lo <= (o.p[0] - pbase) // 4 < hi:
@@ -1567,7 +1651,7 @@ class Engine:
         lo, hi = segs[-1][2], segs[-1][3]
         last_opt, last_pack = OpList(), OpList()
         o0 = opt.ops[0]
-        ptrs = [(o0.p[j] + 4 * lo) if o0.p[j] else None for j in range(4 if self.optimizer != 'sgd' else 3)]
+        ptrs = [(o0.p[j] + 4 * lo) if o0.p[j] else None for j in range(nptr)]
         last_opt.add(o0.kind, opt.tags[0] + '[%d:%d]' % (lo, hi), p=ptrs, i=(hi - lo, int(o0.i[1])), f=tuple(o0.f[j] for j in range(8)))
         sub = OpList()
         for o, tg, mt in zip(pack_ops.ops, pack_ops.tags, pack_ops.meta):
@@ -1653,12 +1737,14 @@ class Engine:
         pl = self.plan(N)
         self.ensure_packed(pl)
         self.make_dropout_mask(N)
+        self._ema_begin_step()
         self.run(pl.fwd_loss)
         from .dp import run_overlapped
         run_overlapped(self.ddp_segments(pl), lambda seg: self.run(seg[0]), self.G, all_reduce, mark)
         self.step_count += 1
         self._set_update(pl.adam_pack.arr[0], 1.0 / world)
         self.run(pl.adam_pack)                    # (Adam, repack, and the step's counters: nbt += 1, loss_sum += loss)
+        self._ema_end_step()
         self.eval_stats_ready = False
         return pl
 
@@ -1863,6 +1949,7 @@ class Engine:
         pl = self.plan(N)
         self.ensure_packed(pl)
         self.make_dropout_mask(N)
+        self._ema_begin_step(update=False)
         self.run(pl.fwd_train)
         self.nbt += 1
         self.eval_stats_ready = False
@@ -1885,15 +1972,20 @@ class Engine:
         self.run(self.plan(N).bwd)
 
     def _set_update(self, op, grad_scale=1.0):
-        """per-step scalars of the optimizer op: the step count (Adam's bias correction) and the gradient scale (1/world)"""
+        """per-step scalars of the optimizer op: the step count (Adam's bias correction), the gradient scale (1/world) and, with a
+        weight average, the weight of this step's update (_ema_begin_step)"""
         op.i[1] = self.step_count
         op.f[3 if self.optimizer == 'sgd' else 5] = grad_scale
+        if self.ema_decay is not None:
+            op.f[4 if self.optimizer == 'sgd' else 6] = self._ema_w
 
     def adam_step(self, N):
         pl = self.plan(N)
         self.step_count += 1
+        self._ema_begin_step()
         self._set_update(pl.adam.arr[0])
         self.run(pl.adam)
+        self._ema_end_step()
         self.packed = False
         self.eval_stats_ready = False
 
@@ -1904,6 +1996,7 @@ class Engine:
         self.ensure_packed(pl)
         self.make_dropout_mask(N)
         self.step_count += 1
+        self._ema_begin_step()
         for j in pl.step_adam_idxs:
             self._set_update(pl.step.arr[j])
         if ev_slot is not None:
@@ -1922,6 +2015,7 @@ class Engine:
             self.run(pl.adam_pack)
         else:
             self.ctx.run_program(pl.step.arr, pl.step.n, self.stream(), op_ms)
+        self._ema_end_step()
         # (nbt += 1 and loss_sum += loss are the step's last op: no framework kernel between load_rois and the end of a step)
         self.eval_stats_ready = False
         return pl

@@ -102,7 +102,12 @@ class HipBackbone(nn.Module):
     def _cbias_pairs(self):
         return [(n.conv_key + '.bias', n.bn_key + '.running_mean') for n in self.engine.convs if getattr(n, 'conv_bias', False)]
 
-    def state_dict(self, *a, **k):
+    def state_dict(self, *a, ema=False, **k):
+        """ema=True (an engine built with ema_decay, TRAIN --ema): the averaged model, as copies -- the tensors of the plain call are
+        views of the engine's buffers, which hold the average only inside ``Engine.ema_weights()``"""
+        if ema:
+            with self.engine.ema_weights():
+                return {key: v.detach().clone() for key, v in self.state_dict(*a, **k).items()}
         sd = super().state_dict(*a, **k)
         prefix = k.get('prefix', a[1] if len(a) > 1 else '')
         for bk, rk in self._cbias_pairs():
@@ -295,12 +300,18 @@ class NeustonModel(nn.Module):
         mp = getattr(hparams, 'mix_prob', None)
         self.mix_prob = 1.0 if mp is None else float(mp)
         self.batch_mix = None             # a neuston_data.BatchMix: fit_batch / fit_batch_ddp then mix every batch they load
+        # additive (TRAIN --ema DECAY): the engine averages the weights inside its fused optimizer step (always with the warm-up); the
+        # fit loop validates, stops, picks and saves the averaged model.  Absent (older files) = off.  The fused path only: the
+        # reference hooks (training_step + a torch optimizer) write P from outside, which restarts the average
+        ema = getattr(hparams, 'ema', None)
+        self.ema = None if ema is None else float(ema)
         self.model = get_namebrand_model(hparams.MODEL, len(hparams.classes), hparams.pretrained, device, mb,
                                          getattr(hparams, 'precision', 'bf16') or 'bf16', optimizer=opt,
                                          lr=float(getattr(hparams, 'learning_rate', None) or 0.001),
                                          momentum=float(getattr(hparams, 'momentum', None) or 0.0), train_batch=train_batch,
                                          class_weights=cw, weight_decay=float(getattr(hparams, 'weight_decay', None) or 0.0),
-                                         label_smoothing=ls, focal_gamma=fg, mix=self.mixup > 0 or self.cutmix > 0)
+                                         label_smoothing=ls, focal_gamma=fg, mix=self.mixup > 0 or self.cutmix > 0,
+                                         **({} if self.ema is None else {'ema_decay': self.ema}))
         # what upstream would have written at neuston_models.py:55; the engine's fused loss ops compute the same weighted, smoothed mean
         eng = self.model.engine
         cwt = None if cw is None else eng.class_weight.clone()

@@ -9,6 +9,7 @@ ifcb_classifier_amd.neuston_net ... TRAIN ...``; ``--batch`` stays per GPU (as u
 ddp_spawn), gradients are averaged over RCCL, BatchNorm statistics stay per rank, rank 0 writes the files.
 """
 import argparse
+import contextlib
 import csv
 import datetime as dt
 import os
@@ -72,6 +73,13 @@ def _focal_gamma(text):
     v = float(text)
     if not 0.0 <= v < float('inf'):            # (nan fails both comparisons)
         raise argparse.ArgumentTypeError('GAMMA must be finite and not negative, got %r' % text)
+    return v
+
+
+def _ema_decay(text):
+    v = float(text)
+    if not 0.0 < v < 1.0:                      # (nan fails both comparisons)
+        raise argparse.ArgumentTypeError('DECAY must be in (0, 1), got %r' % text)
     return v
 
 
@@ -187,37 +195,41 @@ class Trainer:
                 model.fit_current(n, self.world, self._allreduce if self.world > 1 else None)
                 global_step += 1
             model.agg_train_loss = model.epoch_train_loss()
-            steps = []
-            n_next = None
-            for (rois, targets, paths), nxt in self._lookahead(val_loader):
-                n = model.stage_batch(rois, vtf, targets) if n_next is None else n_next
-                model.use_staged()
-                n_next = model.stage_batch(nxt[0], vtf, nxt[1]) if nxt is not None else None
-                probs, loss = model.eval_current(n, with_loss=True)
-                tg = targets.to(dev, non_blocking=True)
-                steps.append(dict(val_batch_loss=loss, val_outputs=probs, val_input_classes=tg, val_input_srcs=list(paths)))
-            steps = self._gather_val(steps, len(val_loader.dataset))
-            stop = False
-            if self.rank == 0:
-                model.validation_epoch_end(steps)
-                log = model.logged
-                self.metrics.append({k: (float(v) if not isinstance(v, bool) else v) for k, v in log.items()
-                                     if k not in ('input_classes', 'output_classes', 'input_srcs', 'outputs')})
-                for cb in self.callbacks:
-                    cb.on_validation_end(log, model, train_loader.dataset, val_loader.dataset)
-                if log['val_loss'] < best:
-                    best, wait = log['val_loss'], 0
-                    if self.world > 1:
-                        pass                                  # rank-0 BN buffers win (DDP broadcast_buffers)
-                    os.makedirs(chk, exist_ok=True)
-                    path = os.path.join(chk, 'epoch={}-step={}.ckpt'.format(epoch, global_step - 1))
-                    torch.save(model.checkpoint_dict(epoch, global_step), path)
-                    if self.best_model_path and os.path.exists(self.best_model_path) and self.best_model_path != path:
-                        os.remove(self.best_model_path)
-                    self.best_model_path = path
-                else:
-                    wait += 1
-                stop = bool(self.estop and wait >= self.estop and epoch + 1 >= self.min_epochs)
+            # TRAIN --ema: the averaged model stands in P / RB from here to the checkpoint -- val_loss, F1 and the results files, early
+            # stopping, the choice of the best epoch and the state_dict saved for it are the averaged model's; training goes on from the
+            # raw weights.  Data parallel: every rank holds the same P after the exchange, so the same average; it is never communicated
+            with (eng.ema_weights() if getattr(eng, 'ema_decay', None) is not None else contextlib.nullcontext()):
+                steps = []
+                n_next = None
+                for (rois, targets, paths), nxt in self._lookahead(val_loader):
+                    n = model.stage_batch(rois, vtf, targets) if n_next is None else n_next
+                    model.use_staged()
+                    n_next = model.stage_batch(nxt[0], vtf, nxt[1]) if nxt is not None else None
+                    probs, loss = model.eval_current(n, with_loss=True)
+                    tg = targets.to(dev, non_blocking=True)
+                    steps.append(dict(val_batch_loss=loss, val_outputs=probs, val_input_classes=tg, val_input_srcs=list(paths)))
+                steps = self._gather_val(steps, len(val_loader.dataset))
+                stop = False
+                if self.rank == 0:
+                    model.validation_epoch_end(steps)
+                    log = model.logged
+                    self.metrics.append({k: (float(v) if not isinstance(v, bool) else v) for k, v in log.items()
+                                         if k not in ('input_classes', 'output_classes', 'input_srcs', 'outputs')})
+                    for cb in self.callbacks:
+                        cb.on_validation_end(log, model, train_loader.dataset, val_loader.dataset)
+                    if log['val_loss'] < best:
+                        best, wait = log['val_loss'], 0
+                        if self.world > 1:
+                            pass                                  # rank-0 BN buffers win (DDP broadcast_buffers)
+                        os.makedirs(chk, exist_ok=True)
+                        path = os.path.join(chk, 'epoch={}-step={}.ckpt'.format(epoch, global_step - 1))
+                        torch.save(model.checkpoint_dict(epoch, global_step), path)
+                        if self.best_model_path and os.path.exists(self.best_model_path) and self.best_model_path != path:
+                            os.remove(self.best_model_path)
+                        self.best_model_path = path
+                    else:
+                        wait += 1
+                    stop = bool(self.estop and wait >= self.estop and epoch + 1 >= self.min_epochs)
             if self.world > 1:
                 flag = torch.tensor([1 if stop else 0], device=dev)
                 self.dist.broadcast(flag, 0)
@@ -404,7 +416,9 @@ def do_training(args):
         # train at, where upstream's dummy input says 244
         from . import onnx_export
         output_path_onnx = os.path.join(args.outdir, args.model_id + '.onnx')
-        onnx_export.export(classifier.model.state_dict(), args.MODEL, args.classes, args.pretrained, output_path_onnx, pad=args.pad)
+        # (TRAIN --ema: the averaged model, as the checkpoint holds)
+        sd = classifier.model.state_dict(ema=True) if classifier.ema is not None else classifier.model.state_dict()
+        onnx_export.export(sd, args.MODEL, args.classes, args.pretrained, output_path_onnx, pad=args.pad)
         print('EXPORTED:', output_path_onnx)
         onnx_export.write_classes(output_path_onnx + '.classes', args.classes)
         print('EXPORTED:', output_path_onnx + '.classes')
@@ -602,6 +616,7 @@ def argparse_nn_train(train_subparser):
     optim.add_argument('--class-norm', metavar='POWER', nargs='?', const=1.0, type=_class_norm_power, default=None, help='Bias results to emphasize smaller classes: weight the loss of class c by n_c^-POWER (n_c: training images of the class), scaled to a mean weight of 1 per training image. POWER defaults to 1 ("balanced"); 0 weights all classes equally. Default (unset) is the unweighted loss')
     optim.add_argument('--label-smoothing', metavar='EPS', default=0.0, type=_label_smoothing, action=_ExclusiveLossScalar, help='Label smoothing of the loss, as nn.CrossEntropyLoss(label_smoothing=EPS): the target distribution is (1-EPS) one-hot + EPS/C uniform, for noisy annotations. A float in [0, 1]; val_loss follows the smoothed value. Default is 0 (hard labels)')
     optim.add_argument('--focal-gamma', metavar='GAMMA', default=0.0, type=_focal_gamma, action=_ExclusiveLossScalar, help='Focal loss against class imbalance: the loss of an image is scaled by (1 - p)^GAMMA, p the softmax probability of its class, so images the network already classifies confidently count less. A finite float >= 0; composes with --class-norm (its weights are the per-class alpha), not with --label-smoothing; val_loss follows the focal value. Default is 0 (cross-entropy)')
+    optim.add_argument('--ema', metavar='DECAY', type=_ema_decay, default=None, help='(MI355X path, additive) Keep an exponential moving average of the weights and of the BatchNorm running statistics, updated inside the fused optimizer step: avg += (1 - d) * (weights - avg) after every step, d = min(DECAY, (1 + t) / (10 + t)) at the t-th step (the warm-up of TensorFlow\'s ExponentialMovingAverage), as torch.optim.swa_utils.get_ema_multi_avg_fn / timm\'s ModelEmaV3. Validation (val_loss, F1, --results files), early stopping, the choice of the best epoch, the saved model and --onnx then use the averaged weights; the training trajectory is unchanged. A float in (0, 1), e.g. 0.999. Default (unset) is no averaging')
     meta = t.add_argument_group(title='Metadata and Annotations')
     meta.add_argument('--dataset-id', help='Associate a dataset id label with this model')
     meta.add_argument('--notes', help='Add any kind of note to the trained model.')

@@ -273,6 +273,20 @@ IFCBK_API int ifcbk_adam_flat(ifcbk_ctx*, float* p, const float* g, float* m, fl
                     void* stream);
 IFCBK_API int ifcbk_sgd_flat(ifcbk_ctx*, float* p, const float* g, float* mom, int64_t n, float lr, float momentum,
                    float weight_decay, float grad_scale, void* stream);
+/* The same steps with an exponential moving average of the weights (TRAIN --ema) taken inside the kernel: after p[i] is updated,
+ * ema[i] <- ema[i] + ema_w * (p[i] - ema[i]) in fp32, from the p held in registers (8 B per element on top of the step's own traffic,
+ * where a pass of its own moves 12).  ema_w = 1 - decay, rounded once from a double by the caller: the lerp form of torch's
+ * swa_utils.get_ema_multi_avg_fn, whose fixed point is p itself.  ema == NULL is ifcbk_adam_flat / ifcbk_sgd_flat, bit for bit (they
+ * are this call); ema_w == 0 leaves ema's bits alone.  IFCBK_EINVAL: ema given with ema_w outside [0, 1] or NaN, or (Adam, 16-byte
+ * accesses) aligned differently from p.                                                                                          */
+IFCBK_API int ifcbk_adam_ema_flat(ifcbk_ctx*, float* p, const float* g, float* m, float* v, float* ema /*nullable*/, int64_t n, float lr,
+                    float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale, float ema_w,
+                    void* stream);
+IFCBK_API int ifcbk_sgd_ema_flat(ifcbk_ctx*, float* p, const float* g, float* mom, float* ema /*nullable*/, int64_t n, float lr,
+                   float momentum, float weight_decay, float grad_scale, float ema_w, void* stream);
+/* the plain update e[i] <- e[i] + w * (x[i] - e[i]) over n fp32 elements, for what no optimizer kernel streams (the BatchNorm running
+ * statistics).  e and x 16-byte aligned; IFCBK_EINVAL: NULL e or x, n < 0, w outside [0, 1] or NaN.  w == 0 or n == 0 launch nothing. */
+IFCBK_API int ifcbk_ema_flat(ifcbk_ctx*, float* e, const float* x, int64_t n, float w, void* stream);
 
 /* ------------------------------------------------------------------ input path
  * replaces PIL convert('RGB') + transforms.Resize([S,S]) (PIL bilinear, antialiased, 8-bit fixed point)
@@ -446,7 +460,10 @@ enum {
     IFCBK_OP_WEIGHT_PACK_MULTI, IFCBK_OP_CONV_WGRAD_SEG, IFCBK_OP_BN_APPLY_MAXPOOL, IFCBK_OP_BN_BWD_MAXPOOL,
     IFCBK_OP_CONV_DGRAD_BNSTAT, IFCBK_OP_BN_BWD_PARTIALS, IFCBK_OP_BN_STATS, IFCBK_OP_AVGPOOL_AFFINE,
     IFCBK_OP_CONV_FWD_AFFINE_SEG,
-    IFCBK_OP_SGD,            /* p: P, G, momentum buffer (nullable); i[0] = n; f: lr, momentum, weight decay, grad scale */
+    IFCBK_OP_SGD,            /* p: P, G, momentum buffer (nullable); i[0] = n; f: lr, momentum, weight decay, grad scale.
+                              * p[3] = the weight average's slice (nullable), f[4] = ema_w: ifcbk_sgd_ema_flat.  IFCBK_OP_ADAM (p: P, G, M,
+                              * V; i: n, step; f: lr, beta1, beta2, eps, weight decay, grad scale) takes them as p[4] and f[6]:
+                              * ifcbk_adam_ema_flat.  NULL, what a zeroed op holds, is the step without an average                */
     IFCBK_OP_RETIRED_31,     /* retired (was the per-chunk-table dgrad + BatchNorm-backward sums); the slot keeps the numbering */
     IFCBK_OP_BIAS_RELU_BWD,  /* p: y, dy, dz, dbias; u.bn: M, C, ldx = ld(y), ldy = ld(dy), relu, dtype; i[0] = ld(dz)          */
     IFCBK_OP_DROPOUT,        /* p: x, mask (nullable), y; i[0] = n, i[1] = dtype; f[0] = scale; flags bit 0 accumulate           */
