@@ -649,9 +649,11 @@ class Engine:
         self.draw = [torch.zeros(Nt * max_raw, dtype=bf, device=dev) for _ in range(self.NL)]
         gmax = max([g.x.H * g.x.W * g.Ktot for g in self.groups] + [0])
         self.draw_group = torch.zeros(max(1, Nt * gmax), dtype=bf, device=dev)
-        mb = max([self.ctx.lib.ifcbk_conv2d_fwd_mblocks(C.byref(self._conv_desc(n, N))) * 2 * n.K for n in self.convs] +
-                 [self.ctx.lib.ifcbk_conv2d_fwd_mblocks(C.byref(self._group_desc(g, N))) * 2 * g.Ktot for g in self.groups] +
-                 [self.ctx.lib.ifcbk_bn_stats_rows(N * n.x.H * n.x.W) * 2 * n.K for n in self.bnrs] + [16])
+        # partial BatchNorm sums, per lane: rows x 2 x channels of the largest layer -- over EVERY batch a plan can be built for, not
+        # the capacity alone.  The row count follows the kernel the library picks for a batch, so it is not monotonic: resnet18 takes
+        # 125,440 floats at batch 5 and 100,352 at batch 8, and the partial last batch of an epoch runs on these buffers
+        # (tests/test_engine_life_cpu.py)
+        mb = max(self._bn_part_floats(b) for b in self._plan_batches())
         self.bn_part = [torch.zeros(mb, dtype=torch.float32, device=dev) for _ in range(self.NL)]
         self.argmax = {}
         for k, n in enumerate(net.nodes):
@@ -695,24 +697,62 @@ class Engine:
             # one factor per image and input slot, 1 = unmixed; the loss ops of a slot's plans (and the graphs captured from them) hold
             # the array's address, which is why the factors live on the device and not in the ops' f[]
             self.mix_lam = [torch.ones(N, dtype=torch.float32, device=dev) for _ in range(2)]
-        # workspace: wgrad split-K slabs / bn_bwd partials
-        ws = 1 << 20
+        # workspace: wgrad split-K slabs / bn_bwd partials -- again over every trainable batch: the split-K depth follows the batch, and
+        # resnet18's weight gradients take 12,544,000 bytes at batch 7 and 12,142,592 at batch 8 (a step at 7 on an engine of capacity
+        # 8 was refused with IFCBK_ENOMEM)
+        self.ctx.reserve(max([1 << 20] + [self._train_workspace(b) for b in range(1, Nt + 1)]))
+
+    def _plan_batches(self):
+        """every batch whose plan touches the training-side scratch (1 .. train_batch), and the capacity"""
+        return list(range(1, self.train_batch + 1)) + ([self.max_batch] if self.max_batch > self.train_batch else [])
+
+    def _bn_part_floats(self, N):
+        """floats one lane's partial-sum buffer must hold for a plan at batch N (every producer of partial rows in _build)"""
+        lib = self.ctx.lib
+        need = [16]
         for n in self.convs:
-            d = self._conv_desc(n, Nt)
-            ws = max(ws, self.ctx.lib.ifcbk_conv2d_wgrad_workspace(C.byref(d)))
+            d = self._conv_desc(n, N)
+            need.append(lib.ifcbk_conv2d_fwd_mblocks(C.byref(d)) * 2 * n.K)
+            need.append(max(0, lib.ifcbk_conv2d_dgrad_bnstat_mblocks(C.byref(d))) * 2 * n.x.C)       # its producer's sums, in its dgrad
+            if n.x.buf.is_input:
+                need.append(max(0, lib.ifcbk_stem_u8_rows(C.byref(d))) * 2 * n.K)
+        for g in self.groups:
+            need.append(lib.ifcbk_conv2d_fwd_mblocks(C.byref(self._group_desc(g, N))) * 2 * g.Ktot)
+        for n in self.bnrs:
+            need.append(lib.ifcbk_bn_stats_rows(N * n.x.H * n.x.W) * 2 * n.K)
+        return max(need)
+
+    def _train_workspace(self, Nt):
+        """bytes of ctx workspace (per lane) the backward ops of a plan at batch Nt ask for"""
+        lib = self.ctx.lib
+        ws = 0
+        for n in self.convs:
+            ws = max(ws, lib.ifcbk_conv2d_wgrad_workspace(C.byref(self._conv_desc(n, Nt))))
             M = Nt * n.P * n.Q
             ws = max(ws, (((M + 255) // 256) * 2 * n.K + 2 * n.K) * 4)
         for g in self.groups:
-            ws = max(ws, self.ctx.lib.ifcbk_conv2d_wgrad_workspace(C.byref(self._group_desc(g, Nt))))
+            ws = max(ws, lib.ifcbk_conv2d_wgrad_workspace(C.byref(self._group_desc(g, Nt))))
         for n in self.plains:
-            ws = max(ws, self.ctx.lib.ifcbk_conv2d_wgrad_workspace(C.byref(self._conv_desc(n, Nt))),
-                     self.ctx.lib.ifcbk_bias_relu_bwd_workspace(Nt * n.P * n.Q, n.K))
+            ws = max(ws, lib.ifcbk_conv2d_wgrad_workspace(C.byref(self._conv_desc(n, Nt))),
+                     lib.ifcbk_bias_relu_bwd_workspace(Nt * n.P * n.Q, n.K))
         for n in self.bnrs:
             M = Nt * n.x.H * n.x.W
             ws = max(ws, (((M + 255) // 256) * 2 * n.K + 2 * n.K) * 4)
         if self.stem_u8 is not None:
-            ws = max(ws, self.ctx.lib.ifcbk_stem_u8_wgrad_workspace(C.byref(self._conv_desc(self.stem_u8, Nt))))
-        self.ctx.reserve(ws)
+            ws = max(ws, lib.ifcbk_stem_u8_wgrad_workspace(C.byref(self._conv_desc(self.stem_u8, Nt))))
+        return ws
+
+    def _grow_workspace(self, ctx, need):
+        """reserve `need` bytes per lane if the ctx holds less.  A growth of the engine's own ctx moves its arenas: the graphs captured
+        so far hold stale pointers (ifcbk_graph_launch would refuse them), so they are destroyed and captured again on next use"""
+        if self.plan_only or need <= ctx.lib.ifcbk_ctx_workspace_bytes(ctx.h):
+            return
+        ctx.reserve(need)
+        if ctx is self.ctx:
+            for pl in self._plans.values():
+                for g in pl.graphs.values():
+                    ctx.lib.ifcbk_graph_destroy(ctx.h, g)
+                pl.graphs.clear()
 
     @property
     def target(self):
@@ -1298,9 +1338,8 @@ class Engine:
                     for m in part:
                         wg_of[m[0]] = grp_obj
             if wg_groups:
-                need = max(gq['ws'] for gq in wg_groups)
-                if not self.plan_only and need > self.ctx.lib.ifcbk_ctx_workspace_bytes(self.ctx.h):
-                    self.ctx.reserve(need)
+                # (a growth here moves the arenas under the graphs of the plans built so far: _grow_workspace drops them)
+                self._grow_workspace(self.ctx, max(gq['ws'] for gq in wg_groups))
                 for gq in wg_groups:
                     for m in gq['members']:
                         own_draw(m)
@@ -1856,12 +1895,7 @@ class Engine:
         if need > ctx.lib.ifcbk_ctx_workspace_bytes(ctx.h):
             if not main:
                 self.pre_stream.synchronize()        # an earlier prefetch may still read the arena that is about to move
-            ctx.reserve(need)
-            if main:
-                for pl in self._plans.values():          # the workspace moved: graphs captured so far hold stale pointers
-                    for g in pl.graphs.values():
-                        self.ctx.lib.ifcbk_graph_destroy(self.ctx.h, g)
-                    pl.graphs.clear()
+            self._grow_workspace(ctx, need)              # (the engine's own ctx: graphs captured so far hold stale pointers and go)
         if jitter is not None:
             # in place on the uploaded blob, stream-ordered in front of the resize (its sums lie where the resize puts its tables)
             ctx.call('ifcbk_roi_jitter', _vp(pixels), _vp(offs), _vp(hs), _vp(ws), n, int(in_channels), int(max_h), int(max_w),

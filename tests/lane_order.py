@@ -85,6 +85,20 @@ def _nan(t):
         raise TypeError(t.dtype)
 
 
+def nan_fill(t):
+    """the poison of a floating buffer, also for a slice of one (the rows behind a partial batch: tests/engine_life.py)"""
+    _nan(t)
+
+
+def holds_nan_fill(t):
+    """every element still is the pattern nan_fill wrote"""
+    if t.dtype == torch.bfloat16:
+        return bool((t.view(torch.int16) == 0x7fc1).all())
+    if t.dtype == torch.float32:
+        return bool((t.view(torch.int32) == 0x7fc00001).all())
+    raise TypeError(t.dtype)
+
+
 def produced_buffers(eng):
     """-> ([(name, floating tensor)], [(name, integer tensor)]) of everything a train step or an eval forward writes"""
     fl, it = [], []
@@ -160,6 +174,13 @@ def outcome(eng):
     for h in eng.heads:
         out[h.name + '.logits'] = h.logits
     return {k: v.clone() for k, v in out.items()}
+
+
+def step_outcome(eng):
+    """outcome plus the bookkeeping a step's last op writes: num_batches_tracked of every BatchNorm and the running loss sum"""
+    out = outcome(eng)
+    out['nbt'], out['loss_sum'] = eng.nbt.clone(), eng.loss_sum.clone()
+    return out
 
 
 def same_bits(a, b):

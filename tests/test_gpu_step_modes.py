@@ -34,10 +34,7 @@ class Rig:
     pass
 
 
-def outcome(eng):
-    out = lo.outcome(eng)
-    out['nbt'], out['loss_sum'] = eng.nbt.clone(), eng.loss_sum.clone()
-    return out
+outcome = lo.step_outcome                                                    # lo.outcome plus nbt and loss_sum (shared with tests/engine_life.py)
 
 
 @pytest.fixture(scope='module')
