@@ -176,6 +176,102 @@ class BatchMix:
         return box_lam(box, S), box
 
 
+def parse_affine(rotate=None, translate=None, scale=None):
+    """the ranges of a random affine (``RandomAffine(degrees=DEG, translate=(T, T), scale=(LO, HI))``) -> None (nothing set: also for
+    0, 0 and 1:1) or (DEG, T, LO, HI).  Host arithmetic only so far: no kernel applies the draw yet, and TRAIN has no flag for it.  DEG finite and >= 0, 0 <= T <= 1, 0.25 <= LO <= HI <= 4: with these every matrix a draw can give stays inside
+    the range of Pillow's 16.16 fixed-point routine.  scale: None, a 'LO:HI' string, one number (LO = HI) or a (LO, HI) pair."""
+    def num(v, what):
+        if isinstance(v, bool):
+            raise ValueError('%s: a number expected, got %r' % (what, v))
+        return float(v)                                                 # (float('a') raises ValueError too)
+    deg = 0.0 if rotate is None else num(rotate, 'rotate')
+    if not 0.0 <= deg < float('inf'):                                   # (nan fails both comparisons)
+        raise ValueError('rotate: DEG must be finite and not negative, got %r' % (rotate,))
+    t = 0.0 if translate is None else num(translate, 'translate')
+    if not 0.0 <= t <= 1.0:
+        raise ValueError('translate: FRAC must be in [0, 1], got %r' % (translate,))
+    if scale is None:
+        lo = hi = 1.0
+    else:
+        if isinstance(scale, str):
+            parts = scale.split(':')
+        elif isinstance(scale, (list, tuple)):
+            parts = list(scale)
+        else:
+            parts = [scale]
+        if not 1 <= len(parts) <= 2:
+            raise ValueError('scale: LO:HI expected, got %r' % (scale,))
+        lo, hi = (num(v, 'scale') for v in (parts[0], parts[-1]))
+        if not 0.25 <= lo <= hi <= 4.0:
+            raise ValueError('scale: 0.25 <= LO <= HI <= 4 expected, got %r' % (scale,))
+    if deg == 0.0 and t == 0.0 and lo == 1.0 and hi == 1.0:
+        return None
+    return deg, t, lo, hi
+
+
+def affine_matrix(S, angle, translate, scale):
+    """torchvision's ``_get_inverse_affine_matrix`` about the centre (S * 0.5, S * 0.5) with no shear: the six floats that
+    ``RandomAffine`` hands to ``Image.transform((S, S), AFFINE, m, NEAREST)``; angle in degrees, translate = (tx, ty) in pixels"""
+    import math
+    rot = math.radians(angle)
+    cx = cy = S * 0.5
+    tx, ty = translate
+    cs, sn = math.cos(rot), math.sin(rot)
+    m = [v / scale for v in (cs, sn, 0.0, -sn, cs, 0.0)]
+    m[2] += m[0] * (-cx - tx) + m[1] * (-cy - ty)
+    m[5] += m[3] * (-cx - tx) + m[4] * (-cy - ty)
+    m[2] += cx
+    m[5] += cy
+    return m
+
+
+def affine_coefs(S, angle, translate, scale):
+    """the six 16.16 fixed-point integers of Pillow's nearest-neighbour affine for one image: Pillow's ``FIX(v) = floor(v * 65536.0 + 0.5)`` of
+    ``affine_matrix``, the half-pixel centre folded into the two offsets.  ValueError when one does not fit an int32."""
+    import math
+    m = affine_matrix(S, angle, translate, scale)
+    fix = lambda v: int(math.floor(v * 65536.0 + 0.5))
+    c = [fix(m[0]), fix(m[1]), fix(m[2] + m[0] * 0.5 + m[1] * 0.5), fix(m[3]), fix(m[4]), fix(m[5] + m[3] * 0.5 + m[4] * 0.5)]
+    if not all(-2 ** 31 <= v < 2 ** 31 for v in c):
+        raise ValueError('affine_coefs: S %d, angle %r, translate %r, scale %r do not fit 16.16 fixed point' % (S, angle, translate, scale))
+    return c
+
+
+AFFINE_IDENTITY = (65536, 0, 32768, 0, 65536, 32768)
+
+
+class AffineDraw:
+    """The per-image draw of a random affine, after torchvision's ``RandomAffine.get_params``: angle ~ U(-DEG, DEG),
+    tx, ty = round(U(-T, T) * S), scale ~ U(LO, HI).  ``fill``: 'border' or a level 0..255 for what the warp uncovers.  The draws come from a
+    generator of this object's own, seeded from (seed, rank): neither ``random`` nor the global numpy / torch streams are touched."""
+
+    def __init__(self, rotate=0.0, translate=0.0, scale=None, fill='border', seed=0, rank=0):
+        p = parse_affine(rotate, translate, scale)
+        if p is None:
+            raise ValueError('AffineDraw: one of rotate, translate and scale must be set')
+        self.deg, self.t, self.lo, self.hi = p
+        self.fill = parse_pad(fill)
+        if self.fill is None:
+            raise ValueError("AffineDraw: fill is 'border' or an integer 0..255")
+        self.rng = np.random.Generator(np.random.PCG64(np.random.SeedSequence([0x616666, int(seed or 0) & 0xffffffffffffffff, int(rank)])))
+
+    def params(self, n, S):
+        """-> n tuples (angle, (tx, ty), scale).  Order of the draws: the n angles (only with DEG > 0), the n tx then the n ty (only with
+        T > 0), the n scales (only with LO < HI)."""
+        ang = self.rng.uniform(-self.deg, self.deg, n) if self.deg > 0 else np.zeros(n)
+        if self.t > 0:
+            tx = np.rint(self.rng.uniform(-self.t, self.t, n) * S)
+            ty = np.rint(self.rng.uniform(-self.t, self.t, n) * S)
+        else:
+            tx = ty = np.zeros(n)
+        sc = self.rng.uniform(self.lo, self.hi, n) if self.lo < self.hi else np.full(n, self.lo)
+        return [(float(ang[i]), (int(tx[i]), int(ty[i])), float(sc[i])) for i in range(n)]
+
+    def draw(self, n, S):
+        """-> int32 tensor [n, 6] (host): ``affine_coefs`` of the draws for a batch of n images"""
+        return torch.tensor([affine_coefs(S, *p) for p in self.params(n, S)], dtype=torch.int32).reshape(n, 6)
+
+
 def parse_pad(value):
     """``--pad [FILL]`` / a checkpoint's ``pad``: None, 'border' or a grey level 0..255 (an int, or its decimal string)"""
     if value is None or value == 'border':
