@@ -16,6 +16,8 @@ address (arg-max planes) with the in-range value 0.  Not poisoned, each for its 
                           zero from allocation and no pack op rewrites them (engine._pack_desc) -- everywhere else Wsh is poisoned
   G between tensors       every tensor of the flat gradient buffer is poisoned, the 16-byte alignment padding between two is not:
                           no op writes it and the optimizer's flat launch reads it (zeros from allocation)
+  G of a vgg*_bn conv bias  in front of a BatchNorm the bias has an identically zero gradient and no op writes it (Engine.cbias_after): like
+                          the padding, zeros from allocation that the optimizer and the data-parallel exchange read
   the ctx workspace       private to the library (per-lane arenas), not reachable from Python
 """
 import ctypes as C
@@ -120,7 +122,8 @@ def produced_buffers(eng):
         if t is not None and (pool is None or t.untyped_storage().data_ptr() != pool.untyped_storage().data_ptr()):
             fl.append(('group[%d].draw_own' % k, t))
     # G per parameter tensor: the alignment padding between two tensors is written by nothing and read by the optimizer's flat launch
-    fl += [('G[%s]' % key, eng.G[o:o + n]) for key, (o, n, _shape, _kind, _node) in eng.poff.items()]
+    # (... and neither is the gradient of a conv bias in front of a BatchNorm)
+    fl += [('G[%s]' % key, eng.G[o:o + n]) for key, (o, n, _shape, kind, _node) in eng.poff.items() if kind != 'bn_cbias']
     fl += [('stats', eng.stats)] + [('bn_part[%d]' % k, t) for k, t in enumerate(eng.bn_part)]
     if all(n.K == n.K_real for n in eng.plains):
         fl.append(('Wsh', eng.Wsh))
