@@ -188,6 +188,66 @@ def test_statistics_sums():
         cb.check_bn_fwd_sums('bn', part, y)
 
 
+# ------------------------------------------------------------------------------------------------------ operands of a layer in a network
+# The twin of test_gpu_conv_f32_bounds.F32['l4ds-net'] (resnet18's layer4.0.downsample.0: 1x1 over 256 channels, fp32): a non-negative
+# post-ReLU input and filters with a common offset.  Every product is then positive: A = sum |x||w| equals |sum x w|, the raw output's
+# mean is several of its standard deviations and the statistics' sums cancel nothing.  The bound must still accept a correct fp32
+# accumulation in any order and still reject one dropped term, one dropped statistics row.
+def _net_case(C=256, K=16, N=2, H=7, W=7, seed=20):
+    g = torch.Generator().manual_seed(seed)
+    x = torch.relu(torch.randn(N, C, H, W, generator=g))
+    w = torch.randn(K, C, 1, 1, generator=g) / C ** 0.5 + 2.0 / C ** 0.5
+    raw = torch.nn.functional.conv2d(x, w)
+    assert float((raw.mean((0, 2, 3)) / raw.std((0, 2, 3))).min()) > 4.0
+    return x, w
+
+
+def test_net_distribution_shuffled_fp32_accumulation_passes_and_a_dropped_term_is_flagged():
+    x, w = _net_case()
+    ref, A, n = cb.fwd(x, w)
+    assert float((A / ref.abs()).max()) < 1.5          # (nothing cancels: the bound is relative to the result itself)
+    prod, shape = _products(x, w, (0, 0))
+    assert cb.check('fwd net', _kernel_like(prod, shape), ref, A, n, out='f32').ratio < 1.0
+    assert cb.check('fwd net', _kernel_like(prod, shape, splits=4), ref, A, n, out='f32').ratio < 1.0
+    m, k = prod.shape[0] // 2, 3
+    prod[m, k, int(prod[m, k].abs().argmax())] = 0    # the largest term of one output element goes missing
+    r = cb.check('fwd net', _kernel_like(prod, shape), ref, A, n, out='f32', raise_=False)
+    assert r.nbad >= 1 and r.ratio > 1.0, r
+
+
+def test_net_distribution_weight_gradient():
+    """fp32 weight gradient of the same layer (N*P*Q = 98, one split in the kernel): the post-ReLU input against a zero-mean upstream
+    gradient; correct passes, a dropped term fails"""
+    x, _ = _net_case()
+    g = torch.Generator().manual_seed(21)
+    N, C, H, W = x.shape
+    K = 8
+    dy = torch.randn(N, K, H, W, generator=g)
+    dy = dy - dy.mean((0, 2, 3), keepdim=True)          # a BatchNorm-backward output has zero per-channel mean
+    ref, A, n = cb.wgrad(x, dy, (K, C, 1, 1))
+    prod = (dy.reshape(N, K, 1, H * W) * x.reshape(N, 1, C, H * W)).permute(1, 2, 0, 3).reshape(K, C, -1)
+    to_krsc = lambda t: t.reshape(K, C, 1, 1).permute(0, 2, 3, 1)
+    assert cb.check('wgrad net', to_krsc(_fp32_sum(prod)), ref, A, n, out='f32', dims=('k', 'r', 's', 'c')).ratio < 1.0
+    bad = prod.clone()
+    bad[3, 50, int(bad[3, 50].abs().argmax())] = 0
+    r = cb.check('wgrad net', to_krsc(_fp32_sum(bad)), ref, A, n, out='f32', dims=('k', 'r', 's', 'c'), raise_=False)
+    assert r.nbad >= 1, r
+
+
+def test_net_distribution_statistics_sums():
+    x, w = _net_case(N=6, H=14, W=14, K=24)
+    y = torch.nn.functional.conv2d(x, w).permute(0, 2, 3, 1).reshape(-1, 24)          # 1176 rows, mean >> spread
+    part = torch.stack([torch.stack([c.sum(0), (c * c).sum(0)]) for c in y.split(128)])     # fp32 partial rows
+    cb.check_bn_fwd_sums('bn net', part, y)
+    part[7, :, 3] = 0                                  # one partial row of one channel not written
+    with pytest.raises(AssertionError, match='sum: 1 of 24'):
+        cb.check_bn_fwd_sums('bn net', part, y)
+    part = torch.stack([torch.stack([c.sum(0), (c * c).sum(0)]) for c in y.split(128)])
+    part[8, 1, 5] = part[8, 1, 5] * (1 + 2.0 ** -8)     # one row's sum of squares off in its 8th bit (a variance a little large)
+    with pytest.raises(AssertionError, match='sumsq: 1 of 24'):
+        cb.check_bn_fwd_sums('bn net', part, y)
+
+
 # ------------------------------------------------------------------------------------------------------ the u8 stem
 # conv_stem_u8.hip emulated step by step in torch on the CPU (fp32 operations as the kernels order them); the bounds of
 # conv_bounds.stem_u8_fwd / stem_u8_wgrad accept the emulation and reject its subtly wrong variants.

@@ -35,8 +35,9 @@ def pick_tile(K, maxt=4):
 
 
 class Row:
-    def __init__(self, case, roles, Cw=None, ldx=None, ldy=None, xoff=0, yoff=0, ldr=None, roff=0, dmode=0):
+    def __init__(self, case, roles, Cw=None, ldx=None, ldy=None, xoff=0, yoff=0, ldr=None, roff=0, dmode=0, dist='randn'):
         self.case, self.roles, self.Cw = case, roles, Cw or case[1]
+        self.dist = dist      # 'randn', or 'net': the operands of a layer inside a network (run_row)
         N, Cc, H, W, K, R, S, sh, sw, ph, pw = case
         self.ldx, self.ldy, self.xoff, self.yoff = ldx or Cc, ldy or K, xoff, yoff
         self.ldr, self.roff, self.dmode = ldr or K, roff, dmode
@@ -60,6 +61,13 @@ F32 = {
     'mode3': Row((2, 48, 11, 13, 72, 1, 7, 1, 1, 0, 3), ('fwd', 'bnstat', 'dgrad +=', 'wgrad')),
     # K tail: 200 = 128 + 72 columns of the forward (NT = 4) and rows of the weight gradient (MT = 4); its input gradient has NT = 1
     'ktail': Row((2, 24, 9, 9, 200, 3, 3, 1, 1, 1, 1), ('fwd', 'affine+res', 'dgrad', 'wgrad', 'wgrad +='), ldx=32, ldy=208, xoff=4, yoff=8),
+    # resnet18's layer4.0.downsample.0 (1x1 / stride 2, 256 -> 512: the node of the fp64 walk whose dW sits farthest from fp64, 1.6-1.8 x
+    # the reference's distance) at N = 2: the same three kernels and the same single weight-gradient split (98 and 392 pixels are 4 and
+    # 13 steps of 32, both under the 16 that a second split needs; run_row asserts the split), on the operands of a layer inside a
+    # network: a non-negative post-ReLU input and filters with a common offset, so that the raw output's mean is ~6 of its standard
+    # deviations and the statistics' sums cancel nothing; the upstream gradient has zero per-channel mean, as a BatchNorm backward
+    # leaves it, but is otherwise random: its correlation with the input inside a trained network is not reproduced
+    'l4ds-net': Row((2, 256, 14, 14, 512, 1, 1, 2, 2, 0, 0), ('fwd', 'dgrad', 'wgrad'), dmode=1, dist='net'),
 }
 SEG_CASE = (1, 64, 11, 35, 132, 1, 1, 1, 1, 0, 0)          # MODE 4: M = 385, K = 132
 KINDS = {'fwd': ('OP_CONV_FWD', 0, False), 'affine': ('OP_CONV_FWD_AFFINE', 0, False), 'affine+res': ('OP_CONV_FWD_AFFINE', 0, True),
@@ -133,9 +141,17 @@ def run_row(ctx, row, dt, seed, fam, expect=None):
     g = torch.Generator().manual_seed(seed)
     x = _rep(torch.randn(N, Cc, H, W, generator=g), dt)
     w = _rep(torch.randn(K, Cc, R, S, generator=g) / (Cw * R * S) ** 0.5, dt)
+    if row.dist == 'net':
+        x = _rep(torch.relu(x), dt)
+        w = _rep(w + 2.0 / (Cw * R * S) ** 0.5, dt)
     x[:, Cw:] = 0
     w[:, Cw:] = 0
     dy = _rep(torch.randn(N, K, P, Q, generator=g), dt)
+    if row.dist == 'net':
+        raw = torch.nn.functional.conv2d(x, w, None, (sh, sw), (ph, pw))
+        assert float((raw.mean((0, 2, 3)) / raw.std((0, 2, 3))).min()) > 4.0, 'the raw output is not mean >> spread'
+        dy = _rep(dy - dy.mean((0, 2, 3), keepdim=True), dt)
+        assert ctx.lib.ifcbk_conv2d_wgrad_workspace(C.byref(d)) == K * R * S * Cc * 4, 'the weight gradient is no longer one split'
     tag = '%s %s' % (out, row.case)
     for role in row.roles:
         if expect and role in KINDS:
