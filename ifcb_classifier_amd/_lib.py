@@ -20,6 +20,7 @@ if os.environ.get('IFCBK_LIB'):
 
 BF16, F32 = 0, 1
 MIX_U8 = 2                                                        # ifcbk_batch_mix: the u8 plane (the dense kinds are BF16 / F32)
+SYM_HFLIP, SYM_VFLIP, SYM_TRANSPOSE = 1, 2, 4                     # ifcbk_batch_sym: one op per call
 OK, EINVAL, EHIP, ENOMEM, EUNSUPPORTED = 0, -1, -2, -3, -4        # include/ifcbk.h
 
 (OP_CONV_FWD, OP_CONV_DGRAD, OP_CONV_WGRAD, OP_WEIGHT_PACK, OP_BN_FINALIZE, OP_BN_APPLY, OP_BN_BWD,
@@ -143,6 +144,7 @@ _PROTOS = {
     'ifcbk_flatten_chw': (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp]),
     'ifcbk_softmax_xent': (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _i, _vp, _vp]),
     'ifcbk_softmax': (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    'ifcbk_softmax_acc': (_i, [_vp, _vp, _i, _i, _vp, _i, _f, _vp]),
     'ifcbk_softmax_xent_w': (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _vp, _i, _vp, _vp]),
     'ifcbk_softmax_xent_ls': (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _f, _vp, _i, _vp, _vp]),
     'ifcbk_softmax_xent_focal': (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _f, _vp, _i, _vp, _vp]),
@@ -160,6 +162,7 @@ _PROTOS = {
     'ifcbk_roi_jitter': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'ifcbk_roi_jitter_workspace': (_sz, [_i]),
     'ifcbk_batch_mix': (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, _vp]),
+    'ifcbk_batch_sym': (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     'ifcbk_u8_channel_moments': (_i, [_vp, _vp, _i, C.c_int64, _i, _vp, _vp]),
     'ifcbk_stem_u8_rows': (_i, [C.POINTER(ConvDesc)]),
     'ifcbk_stem_u8_fwd': (_i, [_vp, C.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),

@@ -103,6 +103,17 @@ __device__ __forceinline__ float to_f32(float v) { return v; }
 template <class T> __device__ __forceinline__ T from_f32(float v);
 template <> __device__ __forceinline__ bf16_t from_f32<bf16_t>(float v) { return f2bf(v); }
 template <> __device__ __forceinline__ float from_f32<float>(float v) { return v; }
+// one row of softmax(dim = 1) as ifcbk_softmax computes it -- a serial maximum, a serial sum of expf(l_j - max), one reciprocal; the
+// probability of class j is then expf(l[j] - mx) * is.  Shared by softmax_kernel (pool_head.hip) and softmax_acc_kernel (loss.hip), so
+// that the two agree bit for bit.
+__device__ __forceinline__ float softmax_row_norm(const float* l, int NC, float& mx_out) {
+    float mx = -INFINITY;
+    for (int j = 0; j < NC; ++j) mx = fmaxf(mx, l[j]);
+    float s = 0.f;
+    for (int j = 0; j < NC; ++j) s += expf(l[j] - mx);
+    mx_out = mx;
+    return 1.f / s;
+}
 static inline int dtype_esize(int dtype) { return dtype == IFCBK_F32 ? 4 : 2; }
 static inline int dtype_chunk(int dtype) { return dtype == IFCBK_F32 ? 4 : 8; }
 

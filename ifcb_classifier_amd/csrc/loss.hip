@@ -330,9 +330,39 @@ __global__ __launch_bounds__(1024) void softmax_xent_mix_kernel(const float* log
     }
 }
 
+// softmax that adds into a score buffer (RUN --tta: the mean of the softmax outputs over the views of a batch):
+//   acc[n][j] = ((accumulate ? acc[n][j] : 0) + p[n][j]) * scale,   p exactly ifcbk_softmax's value (softmax_row_norm, common.h)
+// softmax_kernel's shape: one thread per row, 64-thread blocks, every element read and written by one thread -- bitwise reproducible.
+// p, the sum and the product are three statements: under -ffp-contract=on nothing contracts across them, so each is one rounding, and
+// accumulate == 0 with scale == 1 stores p's bits (p * 1 is exact).
+__global__ void softmax_acc_kernel(const float* logits, int N, int NC, float* acc, int accumulate, float scale) {
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N) return;
+    const float* l = logits + (size_t)n * NC;
+    float* a = acc + (size_t)n * NC;
+    float mx;
+    const float is = softmax_row_norm(l, NC, mx);
+    for (int j = 0; j < NC; ++j) {
+        const float p = expf(l[j] - mx) * is;
+        float v = p;
+        if (accumulate) v = a[j] + p;
+        a[j] = v * scale;
+    }
+}
+
 }  // namespace
 
 #define ST ((hipStream_t)stream)
+
+extern "C" int ifcbk_softmax_acc(ifcbk_ctx* ctx, const float* logits, int N, int NC, float* acc, int accumulate, float scale, void* stream) {
+    if (!ctx) return IFCBK_EINVAL;
+    if (!logits || !acc) IFCBK_FAIL(ctx, IFCBK_EINVAL, "softmax_acc: NULL operand");
+    if (N < 1 || NC < 1) IFCBK_FAIL(ctx, IFCBK_EINVAL, "softmax_acc: N %d or NC %d < 1", N, NC);
+    if (!(scale > 0.f && scale <= FLT_MAX)) IFCBK_FAIL(ctx, IFCBK_EINVAL, "softmax_acc: scale is not a finite positive number");
+    hipLaunchKernelGGL(softmax_acc_kernel, dim3(cdiv(N, 64)), dim3(64), 0, ST, logits, N, NC, acc, accumulate, scale);
+    IFCBK_LAUNCH_CHECK(ctx, "softmax_acc");
+    return IFCBK_OK;
+}
 
 extern "C" int ifcbk_softmax_xent_w(ifcbk_ctx* ctx, const float* logits, const int64_t* target, const float* class_weight, int N, int NC,
                                     float weight, float* loss_out, int loss_accumulate, float* dlogits, void* stream) {

@@ -599,11 +599,8 @@ __global__ void softmax_kernel(const float* logits, int N, int NC, float* probs)
     int n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= N) return;
     const float* l = logits + (size_t)n * NC;
-    float mx = -INFINITY;
-    for (int j = 0; j < NC; ++j) mx = fmaxf(mx, l[j]);
-    float s = 0.f;
-    for (int j = 0; j < NC; ++j) s += expf(l[j] - mx);
-    float is = 1.f / s;
+    float mx;
+    const float is = softmax_row_norm(l, NC, mx);
     for (int j = 0; j < NC; ++j) probs[(size_t)n * NC + j] = expf(l[j] - mx) * is;
 }
 

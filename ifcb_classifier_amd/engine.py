@@ -1948,6 +1948,38 @@ class Engine:
         ctx.call('ifcbk_batch_mix', _vp(buf), kind, n, self.net.S, _vp(self.mix_lam[s]), y0, y1, x0, x1, stream)
         return n
 
+    # the views of test-time augmentation (RUN --tta) as walks over ifcbk_batch_sym's ops: every step turns the batch into a view not seen
+    # before.  'flips': e, H, VH, V (one more V restores the batch); 'all': with T the transpose, H after T is a quarter turn, so the
+    # alternating walk passes through all eight symmetries of the square (one more H restores)
+    TTA_WALKS = {'flips': (_lib.SYM_HFLIP, _lib.SYM_VFLIP, _lib.SYM_HFLIP),
+                 'all': (_lib.SYM_TRANSPOSE, _lib.SYM_HFLIP) * 3 + (_lib.SYM_TRANSPOSE,)}
+
+    def sym_batch(self, n, op, slot=None):
+        """apply one symmetry (``_lib.SYM_HFLIP`` / ``SYM_VFLIP`` / ``SYM_TRANSPOSE``) to the ``n`` loaded images of an input slot, in
+        place on whichever buffer the slot's load wrote (the u8 plane or the dense tensor): the plans of the slot, and the graphs
+        captured from them, go on reading the same pointers.  slot: as ``mix_batch`` -- None is the current slot on the current
+        stream, a prefetch slot runs on the prefetch stream and context."""
+        n = int(n)
+        if not 1 <= n <= self.max_batch:
+            raise ValueError('sym_batch: n %d outside 1..%d' % (n, self.max_batch))
+        if slot is not None:
+            ctx, stream, s = self.pre_ctx, C.c_void_p(self.pre_stream.cuda_stream), slot
+        else:
+            ctx, stream, s = self.ctx, self.stream(), self.in_slot
+        if self.in_kind[s] == 'u8':
+            buf, kind = self.in_u8[s], _lib.MIX_U8
+        else:
+            buf, kind = self.in_bufs[s], self.cdtype
+        ctx.call('ifcbk_batch_sym', _vp(buf), kind, n, self.net.S, int(op), stream)
+        return n
+
+    def softmax_acc(self, N, first, scale=1.0):
+        """softmax of the main head's logits of the last forward at batch ``N``, added into ``probs`` (``first``: stored instead) and
+        the sum scaled by ``scale`` (ifcbk_softmax_acc), on the current stream.  No op kind, no program: a direct call."""
+        main = [h for h in self.heads if not h.aux][0]
+        self.ctx.call('ifcbk_softmax_acc', _vp(main.logits), int(N), self.net.NC, _vp(self.probs), 0 if first else 1, float(scale),
+                      self.stream())
+
     def make_dropout_mask(self, N):
         ext = self.external_mask
         for h in self.heads:

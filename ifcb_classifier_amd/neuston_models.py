@@ -463,6 +463,27 @@ class NeustonModel(nn.Module):
         eng.run(pl.softmax)
         return eng.probs[:N].clone(), loss
 
+    def eval_current_tta(self, N, mode):
+        """RUN --tta: the class scores of the current batch averaged over symmetry views of the NETWORK INPUT (the S x S batch after the
+        resize, where it lies).  mode 'flips': the 4 views e, H, VH, V; 'all': the 8 symmetries of the square (``Engine.TTA_WALKS``).
+        Eval forward and softmax of the batch as loaded, then per step of the walk one ``Engine.sym_batch``, one eval forward and one
+        accumulating softmax; the last one scales by 1 / V (V = 4 or 8: exact), so the result is the fp32 left-to-right sum of the
+        views' ``eval_current`` scores times 1 / V.  Returns probs[N, NC] (device, a copy).  The input slot is LEFT IN ITS LAST VIEW
+        (the walk is one step short of the identity): RUN never reads a slot again; a caller that does applies one more
+        ``sym_batch`` -- SYM_HFLIP after 'all', SYM_VFLIP after 'flips'."""
+        eng = self.model.engine
+        walk = eng.TTA_WALKS.get(mode)
+        if walk is None:
+            raise ValueError('eval_current_tta: mode %r is not one of %s' % (mode, sorted(eng.TTA_WALKS)))
+        self.model.eval()
+        eng.forward_eval(N)
+        eng.softmax_acc(N, first=True)
+        for k, op in enumerate(walk):
+            eng.sym_batch(N, op)
+            eng.forward_eval(N)
+            eng.softmax_acc(N, first=False, scale=1.0 / (len(walk) + 1) if k == len(walk) - 1 else 1.0)
+        return eng.probs[:N].clone()
+
     def fit_batch_ddp(self, input_data, input_classes, world, all_reduce):
         """data-parallel twin of fit_batch: per-rank local BatchNorm statistics (no SyncBN upstream), gradient
         all-reduce over RCCL launched per finished bucket and overlapped with the rest of backward."""

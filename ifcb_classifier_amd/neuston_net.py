@@ -155,6 +155,13 @@ class Trainer:
         self.metrics = []
         self.best_model_path = None
         self.dist, self.rank, self.world = _dist()
+        self.tta = None                   # RUN --tta: 'flips' / 'all' -- the test loops average each batch's scores over symmetry views
+
+    def _scores(self, model, n):
+        """the class scores of the current batch of the test loops: plain, or (RUN --tta) the mean over the views"""
+        if self.tta is None:
+            return model.eval_current(n)[0]
+        return model.eval_current_tta(n, self.tta)
 
     @staticmethod
     def _lookahead(loader):
@@ -268,7 +275,7 @@ class Trainer:
             n = model.stage_batch(rois, transform) if n_next is None else n_next
             model.use_staged()
             n_next = model.stage_batch(nxt[0], transform) if nxt is not None else None
-            probs, _ = model.eval_current(n)
+            probs = self._scores(model, n)
             steps.append(dict(test_outputs=probs, test_srcs=list(ids)))
         rr = model.test_epoch_end(steps, input_obj)
         rr.type = 'Bin' if hasattr(input_obj, 'yearday') else 'ImgDir'
@@ -292,7 +299,7 @@ class Trainer:
             n = model.stage_resident(res, i0, i1, ds.transform) if n_next is None else n_next
             model.use_staged()
             n_next = model.stage_resident(res, bounds[k + 1][0], bounds[k + 1][1], ds.transform) if k + 1 < len(bounds) else None
-            probs, _ = model.eval_current(n)
+            probs = self._scores(model, n)
             steps.append(dict(test_outputs=probs, test_srcs=list(ds.pids[i0:i1])))
         rr = model.test_epoch_end(steps, input_obj)
         rr.type = 'Bin'
@@ -313,7 +320,7 @@ class Trainer:
             n = model.stage_batch(rois, tf) if n_next is None else n_next
             model.use_staged()
             n_next = model.stage_batch(nxt[0], tf) if nxt is not None else None
-            p, _ = model.eval_current(n)
+            p = self._scores(model, n)
             probs.append(p)
             ids.extend(pids)
         probs = torch.cat(probs, 0).detach().cpu().numpy()
@@ -456,6 +463,7 @@ def do_run(args):
                                  [o for o in args.outfile if o.endswith('.h5')]))
     callbacks = [SaveTestResults(outdir=args.outdir, outfile=o, timestamp=args.cmd_timestamp) for o in args.outfile]
     trainer = Trainer(0, 0, 0, args.outdir)
+    trainer.tta = getattr(args, 'tta', None)
     filter_mode, filter_keywords = None, []
     if args.filter:
         filter_mode = args.filter[0]
@@ -633,6 +641,7 @@ def argparse_nn_run(run_subparser):
     r.add_argument('--filter', nargs='+', metavar=('IN|OUT', 'KEYWORD'), help='Explicitly include (IN) or exclude (OUT) bins or image-files by KEYWORDs.')
     r.add_argument('--clobber', action='store_true', help='If set, already processed bins in OUTDIR are reprocessed.')
     r.add_argument('--gobig', action='store_true', help=argparse.SUPPRESS)
+    r.add_argument('--tta', choices=['flips', 'all'], default=None, help='(MI355X path, additive) Test-time augmentation: the class scores of an image are the mean of the softmax outputs over symmetry views of the resized network input, "flips" = 4 views (identity, both flips, half turn), "all" = the 8 symmetries of the square; for models trained with --flip / --rot90. Costs 4 or 8 forwards per batch; the output files keep their format. Default (unset) is one view')
 
 
 def argparse_nn_runtimeparams(args):

@@ -221,6 +221,12 @@ IFCBK_API int ifcbk_dropout_mask(ifcbk_ctx*, uint8_t* mask, int64_t n, float p, 
 IFCBK_API int ifcbk_softmax_xent(ifcbk_ctx*, const float* logits, const int64_t* target, int N, int NC, float weight,
                        float* loss_out, int loss_accumulate, float* dlogits, void* stream);
 IFCBK_API int ifcbk_softmax(ifcbk_ctx*, const float* logits, int N, int NC, float* probs, void* stream);
+/* softmax added into a score buffer (RUN --tta: the mean of the softmax outputs over the views of a batch), in fp32:
+ * acc[n][j] = ((accumulate ? acc[n][j] : 0) + p[n][j]) * scale, p computed exactly as ifcbk_softmax computes it; the sum and the
+ * product are one rounding each.  accumulate = 0, scale = 1 gives ifcbk_softmax's bits.  A mean over V views: accumulate = 0 for the
+ * first, scale = 1 for all but the last, 1 / V for the last (exact for a power of two).  IFCBK_EINVAL: NULL logits or acc, N or
+ * NC < 1, scale not finite or <= 0.  One thread per row: bitwise reproducible. */
+IFCBK_API int ifcbk_softmax_acc(ifcbk_ctx*, const float* logits, int N, int NC, float* acc, int accumulate, float scale, void* stream);
 /* the same with per-class weights (TRAIN --class-norm): nn.CrossEntropyLoss(weight=class_weight), mean reduction, what upstream
  * would have written at neuston_models.py:55.  W = sum_i class_weight[target_i];
  * loss_out[0] (+)= weight * sum_i class_weight[target_i] CE(logits_i, target_i) / W;
@@ -348,6 +354,20 @@ IFCBK_API int ifcbk_roi_jitter(ifcbk_ctx*, const uint8_t* pixels, const int64_t*
 #define IFCBK_MIX_U8 2
 IFCBK_API int ifcbk_batch_mix(ifcbk_ctx*, void* x, int kind /* IFCBK_MIX_U8 | IFCBK_BF16 | IFCBK_F32 */, int N, int S,
                          const float* lam /*[N], device*/, int y0, int y1, int x0, int x1, void* stream);
+/* one symmetry of the square applied to every image of a RESIZED batch, in place (RUN --tta: the views of test-time augmentation are
+ * taken where the batch lies, so the eval programs and their captured graphs keep their pointers).  x and kind as ifcbk_batch_mix:
+ * the u8 plane [N][S][S] (kind = IFCBK_MIX_U8; any address) or the dense tensor [N][S][S][8] (kind = IFCBK_BF16 / IFCBK_F32; 16-byte
+ * aligned), where a pixel -- 16 bytes in bf16, 32 in fp32 -- moves whole.  op is exactly one of the three below.  The result is an
+ * exact permutation of the input's bytes; every op is its own inverse; S == 1 is a no-op.  With T = TRANSPOSE and H = HFLIP the walk
+ * T, H, T, H, T, H, T passes through the other seven elements of the symmetry group and one more H restores the input (H after T is a
+ * quarter turn); H, V, H walks the flip group and one more V restores.  No byte outside the N images is read or written.
+ * IFCBK_EINVAL: x NULL, N < 1, S < 1 (or > 32768), an unknown kind, an op that is not exactly one of the three, a dense tensor that is
+ * not 16-byte aligned. */
+#define IFCBK_SYM_HFLIP     1   /* x'[n][r][c] = x[n][r][S-1-c] */
+#define IFCBK_SYM_VFLIP     2   /* x'[n][r][c] = x[n][S-1-r][c] */
+#define IFCBK_SYM_TRANSPOSE 4   /* x'[n][r][c] = x[n][c][r]     */
+IFCBK_API int ifcbk_batch_sym(ifcbk_ctx*, void* x, int kind /* IFCBK_MIX_U8 | IFCBK_BF16 | IFCBK_F32 */, int N, int S, int op,
+                         void* stream);
 /* per-image, per-channel integer moments of a u8 plane [n_img][pixels_per_img][channels] (channels 1..4):
    out[i][c][0] = sum of v, out[i][c][1] = sum of v*v, exact (uint64); n_img = 0 is a no-op.
  * x is typically out_u8 of ifcbk_roi_preprocess; mean = sum v / (255 n), population std from the two sums.
