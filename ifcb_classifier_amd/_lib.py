@@ -149,6 +149,7 @@ _PROTOS = {
     'ifcbk_softmax_xent_ls': (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _f, _vp, _i, _vp, _vp]),
     'ifcbk_softmax_xent_focal': (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _f, _vp, _i, _vp, _vp]),
     'ifcbk_softmax_xent_mix': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _vp, _i, _vp, _vp]),
+    'ifcbk_softmax_xent_distill': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _f, _f, _vp, _i, _vp, _vp]),
     'ifcbk_step_counters': (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     'ifcbk_adam_flat': (_i, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _f, _f, _f, _f, _f, _i, _f, _vp]),
     'ifcbk_sgd_flat': (_i, [_vp, _vp, _vp, _vp, C.c_int64, _f, _f, _f, _f, _vp]),

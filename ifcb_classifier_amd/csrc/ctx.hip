@@ -142,6 +142,16 @@ static int run_one(ifcbk_ctx* c, const ifcbk_op* o, void* st) {
     // kernel, with p[4] as the class weights of the _W kind and none for the plain kind; f[1] == 0 takes the cases below untouched
     if ((o->kind == IFCBK_OP_SOFTMAX_XENT || o->kind == IFCBK_OP_SOFTMAX_XENT_W) && o->f[1] != 0.f && o->f[2] != 0.f)
         IFCBK_FAIL(c, IFCBK_EINVAL, "softmax_xent op: label smoothing (f[1]) and focal gamma (f[2]) are both set");
+    // a teacher's logits (TRAIN --distill) ride on them as p[6], with alpha in f[3] and the temperature in f[4]: NULL, what a zeroed op
+    // holds, is every case below untouched; an array sends the op to the distillation kernel with f[1] as its smoothing factor; it
+    // combines with neither focal loss nor a mixed batch
+    if ((o->kind == IFCBK_OP_SOFTMAX_XENT || o->kind == IFCBK_OP_SOFTMAX_XENT_W) && p[6]) {
+        if (o->f[2] != 0.f) IFCBK_FAIL(c, IFCBK_EINVAL, "softmax_xent op: teacher logits (p[6]) and focal gamma (f[2]) are both set");
+        if (p[5]) IFCBK_FAIL(c, IFCBK_EINVAL, "softmax_xent op: teacher logits (p[6]) and mix factors (p[5]) are both set");
+        return ifcbk_softmax_xent_distill(c, (const float*)p[0], (const int64_t*)p[1], (const float*)p[6],
+                                          o->kind == IFCBK_OP_SOFTMAX_XENT_W ? (const float*)p[4] : nullptr, (int)o->i[0], (int)o->i[1], o->f[0],
+                                          o->f[1], o->f[3], o->f[4], (float*)p[2], acc, (float*)p[3], st);
+    }
     // the factors of a mixed batch (TRAIN --mixup / --cutmix) ride on them as p[5]: NULL, what a zeroed op holds, is every case below
     // untouched; an array sends the op to the two-target kernel with f[1] as its smoothing factor; it does not combine with focal loss
     if ((o->kind == IFCBK_OP_SOFTMAX_XENT || o->kind == IFCBK_OP_SOFTMAX_XENT_W) && p[5]) {
@@ -667,7 +677,8 @@ extern "C" int ifcbk_op_kernel(const ifcbk_op* o, char* name, size_t cap) {
         case IFCBK_OP_WEIGHT_PACK: snprintf(name, cap, "weight_pack_kernel"); break;
         case IFCBK_OP_WEIGHT_PACK_MULTI: snprintf(name, cap, "weight_pack_multi_kernel"); break;
         case IFCBK_OP_SOFTMAX_XENT: case IFCBK_OP_SOFTMAX_XENT_W:
-            if (o->p[5]) snprintf(name, cap, "softmax_xent_mix_kernel");          // (the one-target losses stay unnamed, as they were)
+            if (o->p[6]) snprintf(name, cap, "softmax_xent_distill_kernel");
+            else if (o->p[5]) snprintf(name, cap, "softmax_xent_mix_kernel");     // (the one-target losses stay unnamed, as they were)
             break;
         default: break;
     }
@@ -736,7 +747,10 @@ extern "C" int ifcbk_op_cost(const ifcbk_op* o, double* flops, double* bytes) {
         case IFCBK_OP_ADAM: by = (double)o->i[0] * (28 + (o->p[4] ? 8 : 0)); break;      // (+ the weight average: read and written)
         case IFCBK_OP_SGD: by = (double)o->i[0] * ((o->p[2] ? 20 : 12) + (o->p[3] ? 8 : 0)); break;
         case IFCBK_OP_SOFTMAX_XENT: case IFCBK_OP_SOFTMAX_XENT_W:
-            if (o->p[5]) {                  // the two-target loss: logits in, dlogits out (when asked for), targets and factors
+            if (o->p[6]) {                  // the distillation loss: logits and teacher in, dlogits out (when asked for), targets
+                fl = (double)o->i[0] * o->i[1] * 30;
+                by = (double)o->i[0] * o->i[1] * (o->p[3] ? 12 : 8) + (double)o->i[0] * 8;
+            } else if (o->p[5]) {           // the two-target loss: logits in, dlogits out (when asked for), targets and factors
                 fl = (double)o->i[0] * o->i[1] * 12;
                 by = (double)o->i[0] * o->i[1] * (o->p[3] ? 8 : 4) + (double)o->i[0] * 12;
             }

@@ -2,7 +2,8 @@
 // own kernel and entry point (pool_head.hip); this file is reached only when the engine holds class weights -- or a label-smoothing
 // factor (TRAIN --label-smoothing: softmax_xent_ls_kernel, with or without class weights), or a focusing exponent (TRAIN --focal-gamma:
 // softmax_xent_focal_kernel, with or without class weights), or the factors of a mixed batch (TRAIN --mixup / --cutmix:
-// softmax_xent_mix_kernel, two targets per image, with or without class weights and smoothing).
+// softmax_xent_mix_kernel, two targets per image, with or without class weights and smoothing), or a teacher's logits (TRAIN --distill:
+// softmax_xent_distill_kernel, with or without class weights and smoothing).
 #include "common.h"
 #include <float.h>
 #include <math.h>
@@ -330,6 +331,141 @@ __global__ __launch_bounds__(1024) void softmax_xent_mix_kernel(const float* log
     }
 }
 
+// Knowledge distillation (TRAIN --distill): Hinton's loss, the smoothed hard loss of softmax_xent_ls_kernel mixed with the KL divergence
+// from a teacher's softened scores.  a = weight, T = temperature, s = logits, z = teacher, r = softmax(s / T), q = softmax(z / T), and
+// H, Dh = loss and dlogits of softmax_xent_ls_kernel at weight 1 (same class_weight, eps and normaliser W = sum_n w[t_n]):
+//   K       = 1 / N * sum_n sum_j q[n][j] (log q[n][j] - log r[n][j])                        (KL(q || r), "batchmean")
+//   loss    = a * ((1 - alpha) * H + alpha T^2 * K)
+//   d[n][j] = a * ((1 - alpha) * Dh[n][j] + alpha T / N * (r[n][j] - q[n][j]))
+// Class weights act on the hard term only.  softmax_xent_ls_kernel's shape: one 1024-thread block, 4 lanes per sample, fixed butterflies,
+// one fixed-order slot pre-pass for W and SW, fixed-order final sums (one chain of 256 slots for the hard terms, one for the soft ones)
+// -- bitwise reproducible.  Points of the arithmetic:
+//   x / T is a DIVISION of the rounded difference: arg_j = fl(fl(x_j - max) / T), correctly rounded, two roundings per argument (a product
+//     with a rounded 1 / T would be three).  T > 0, so the row's maximum is the maximum of x / T as well and its argument is exactly 0:
+//     both softened sums are >= 1, as s is.
+//   log q - log r is formed from the arguments, never from a stored probability: log q_j = arg_j(z) - log sum_q, each part <= 0, so neither
+//     log-probability cancels; the difference of the two does, which is why the bound is taken on q (|log q| + |log r|).
+//   a q[n][j] that underflows to 0 contributes exactly 0 to the loss (its finite log difference is not multiplied in), and its dlogits
+//     element is a alpha T / N * r[n][j]; no log of 0 is taken anywhere.
+//   alpha == 1: 1 - alpha is an exact 0 and multiplies a finite hard term (W != 0), so without class weights neither output depends on
+//     target; alpha == 0: alpha T^2 and alpha T / N are exact zeros on finite soft terms, so neither output depends on teacher, and
+//     the function is softmax_xent_ls_kernel's (through this kernel's own operations, not its bits).
+//   In dlogits the weight a is folded into the two factors: the hard part is a Dh exactly as softmax_xent_ls_kernel forms it
+//     (g = a / W), the soft factor is fl(a * fl(fl(alpha T) / N)); at alpha == 0 the element is 1 * (a Dh) + 0.
+// Per sample, on top of that kernel: 2 NC divisions, 2 NC expf and 2 logf for the two softened sums, NC (2 subtract, subtract, multiply)
+// + 2 butterfly adds for K, and for dlogits NC (2 expf, 2 multiply, subtract, 2 multiply-add).
+// A target outside [0, NC) is the caller's fault, as there; so is W == 0 (NaN, also at alpha == 1).
+__global__ __launch_bounds__(1024) void softmax_xent_distill_kernel(const float* logits, const int64_t* target, const float* teacher,
+                                                                    const float* class_weight, int N, int NC, float weight, float eps,
+                                                                    float alpha, float T, float* loss_out, int loss_acc, float* dlogits) {
+    __shared__ float sl[256];
+    __shared__ float sk[256];
+    __shared__ float sW[2];
+    const int sub = threadIdx.x & 3, slot = threadIdx.x >> 2;
+    if (sub == 0) {
+        float wsum = 0.f, ksum = 0.f;
+        for (int n = slot; n < N; n += 256) wsum += class_weight ? class_weight[(int)target[n]] : 1.f;
+        for (int k = slot; k < NC; k += 256) ksum += class_weight ? class_weight[k] : 1.f;
+        sl[slot] = wsum;
+        sk[slot] = ksum;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float s = 0.f, k = 0.f;
+        for (int i = 0; i < 256; ++i) s += sl[i];
+        for (int i = 0; i < 256; ++i) k += sk[i];
+        sW[0] = s;
+        sW[1] = k;
+    }
+    __syncthreads();
+    const float W = sW[0], SW = sW[1];
+    const float invW = 1.f / W;
+    const float c1 = 1.f - eps, eC = eps / (float)NC;
+    const float ch = 1.f - alpha;                     // weight of the hard term
+    const float cs = (alpha * T) * T;                 // ... of K in the loss
+    const float cd = weight * ((alpha * T) / (float)N);      // ... of r - q in dlogits, the weight folded in
+    const float g = weight / W;                       // the hard gradient's factor, as softmax_xent_ls_kernel forms it
+    float local = 0.f, localk = 0.f;
+    for (int n0 = 0; n0 < N; n0 += 256) {
+        const int n = n0 + slot;
+        const bool ok = n < N;
+        const float* l = logits + (size_t)(ok ? n : 0) * NC;
+        const float* z = teacher + (size_t)(ok ? n : 0) * NC;
+        float mx = -INFINITY, mz = -INFINITY;
+        for (int j = sub; j < NC; j += 4) {
+            mx = fmaxf(mx, l[j]);
+            mz = fmaxf(mz, z[j]);
+        }
+        mx = fmaxf(mx, __shfl_xor(mx, 1));
+        mx = fmaxf(mx, __shfl_xor(mx, 2));
+        mz = fmaxf(mz, __shfl_xor(mz, 1));
+        mz = fmaxf(mz, __shfl_xor(mz, 2));
+        float s = 0.f, sr = 0.f, sq = 0.f;
+        for (int j = sub; j < NC; j += 4) {
+            const float dl = l[j] - mx, dz = z[j] - mz;
+            s += expf(dl);
+            sr += expf(dl / T);
+            sq += expf(dz / T);
+        }
+        s += __shfl_xor(s, 1);
+        s += __shfl_xor(s, 2);
+        sr += __shfl_xor(sr, 1);
+        sr += __shfl_xor(sr, 2);
+        sq += __shfl_xor(sq, 1);
+        sq += __shfl_xor(sq, 2);
+        const float ls = logf(s), lsr = logf(sr), lsq = logf(sq);
+        const float isr = 1.f / sr, isq = 1.f / sq;
+        float q = 0.f, kl = 0.f;
+        for (int j = sub; j < NC; j += 4) {
+            q += (class_weight ? class_weight[j] : 1.f) * ((mx - l[j]) + ls);
+            const float ar = (l[j] - mx) / T, aq = (z[j] - mz) / T;
+            const float qj = expf(aq) * isq;
+            const float diff = (aq - lsq) - (ar - lsr);
+            const float term = qj * diff;
+            kl += qj > 0.f ? term : 0.f;
+        }
+        q += __shfl_xor(q, 1);
+        q += __shfl_xor(q, 2);
+        kl += __shfl_xor(kl, 1);
+        kl += __shfl_xor(kl, 2);
+        const int tg = ok ? (int)target[n] : 0;
+        const float wt = ok ? (class_weight ? class_weight[tg] : 1.f) : 0.f;
+        const float hard = c1 * wt;
+        if (ok && sub == 0) {
+            const float li = mx + ls - l[tg];
+            local += c1 * (wt * li) + eC * q;
+            localk += kl;
+        }
+        if (ok && dlogits) {
+            float* d = dlogits + (size_t)n * NC;
+            const float is = 1.f / s;
+            const float A = hard + eC * SW;
+            for (int j = sub; j < NC; j += 4) {
+                const float dh = g * (A * (expf(l[j] - mx) * is) - (j == tg ? hard : 0.f) - eC * (class_weight ? class_weight[j] : 1.f));
+                const float rj = expf((l[j] - mx) / T) * isr, qj = expf((z[j] - mz) / T) * isq;
+                const float soft = cd * (rj - qj);
+                d[j] = ch * dh + soft;
+            }
+        }
+    }
+    __syncthreads();                       // (thread 0 has finished reading the pre-pass partials)
+    if (sub == 0) {
+        sl[slot] = local;
+        sk[slot] = localk;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float s = 0.f, k = 0.f;
+        for (int i = 0; i < 256; ++i) s += sl[i];
+        for (int i = 0; i < 256; ++i) k += sk[i];
+        const float H = s * invW;
+        const float K = k * (1.f / (float)N);
+        const float soft = cs * K;
+        const float v = weight * (ch * H + soft);
+        loss_out[0] = loss_acc ? loss_out[0] + v : v;
+    }
+}
+
 // softmax that adds into a score buffer (RUN --tta: the mean of the softmax outputs over the views of a batch):
 //   acc[n][j] = ((accumulate ? acc[n][j] : 0) + p[n][j]) * scale,   p exactly ifcbk_softmax's value (softmax_row_norm, common.h)
 // softmax_kernel's shape: one thread per row, 64-thread blocks, every element read and written by one thread -- bitwise reproducible.
@@ -408,5 +544,20 @@ extern "C" int ifcbk_softmax_xent_mix(ifcbk_ctx* ctx, const float* logits, const
     hipLaunchKernelGGL(softmax_xent_mix_kernel, dim3(1), dim3(1024), 0, ST, logits, target, lam, class_weight, N, NC, weight, label_smoothing,
                        loss_out, loss_accumulate, dlogits);
     IFCBK_LAUNCH_CHECK(ctx, "softmax_xent_mix");
+    return IFCBK_OK;
+}
+
+extern "C" int ifcbk_softmax_xent_distill(ifcbk_ctx* ctx, const float* logits, const int64_t* target, const float* teacher,
+                                          const float* class_weight, int N, int NC, float weight, float label_smoothing, float alpha,
+                                          float temperature, float* loss_out, int loss_accumulate, float* dlogits, void* stream) {
+    if (N <= 0 || NC <= 0) IFCBK_FAIL(ctx, IFCBK_EINVAL, "softmax_xent_distill: empty");
+    if (!teacher) IFCBK_FAIL(ctx, IFCBK_EINVAL, "softmax_xent_distill: teacher is NULL (the losses without a teacher are ifcbk_softmax_xent_w / _ls)");
+    if (!(label_smoothing >= 0.f && label_smoothing <= 1.f)) IFCBK_FAIL(ctx, IFCBK_EINVAL, "softmax_xent_distill: label_smoothing outside [0, 1]");
+    if (!(alpha >= 0.f && alpha <= 1.f)) IFCBK_FAIL(ctx, IFCBK_EINVAL, "softmax_xent_distill: alpha outside [0, 1]");
+    if (!(temperature > 0.f && temperature <= FLT_MAX)) IFCBK_FAIL(ctx, IFCBK_EINVAL, "softmax_xent_distill: temperature is not a finite positive number");
+    if (!logits || !target || !loss_out) IFCBK_FAIL(ctx, IFCBK_EINVAL, "softmax_xent_distill: NULL operand");
+    hipLaunchKernelGGL(softmax_xent_distill_kernel, dim3(1), dim3(1024), 0, ST, logits, target, teacher, class_weight, N, NC, weight,
+                       label_smoothing, alpha, temperature, loss_out, loss_accumulate, dlogits);
+    IFCBK_LAUNCH_CHECK(ctx, "softmax_xent_distill");
     return IFCBK_OK;
 }

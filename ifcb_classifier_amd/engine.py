@@ -183,6 +183,26 @@ def _index_bytes():
     return int(float(e) * (1 << 30)) if e else VERIFIED_ACTIVATION_BYTES
 
 
+def check_distill(distill, focal_gamma=0.0, mix=False):
+    """the ``distill`` argument of Engine: None, or (alpha, T) with alpha in [0, 1] and T finite and > 0 -> None or a tuple of two floats.
+    Distillation combines with neither focal loss nor a mixed batch (the library refuses such an op as well)."""
+    if distill is None:
+        return None
+    try:
+        alpha, T = (float(v) for v in distill)
+    except (TypeError, ValueError):
+        raise ValueError('distill must be None or (alpha, temperature), got %r' % (distill,)) from None
+    if not 0.0 <= alpha <= 1.0:                                   # (a NaN fails both comparisons)
+        raise ValueError('distill: alpha must be in [0, 1]')
+    if not 0.0 < T < math.inf:
+        raise ValueError('distill: the temperature must be finite and > 0')
+    if focal_gamma and focal_gamma > 0:
+        raise ValueError('distill and focal_gamma do not combine: give one of them')
+    if mix:
+        raise ValueError('distill and mix do not combine: give one of them')
+    return alpha, T
+
+
 class Engine:
     """Device state of one model replica."""
 
@@ -194,7 +214,7 @@ class Engine:
 
     def __init__(self, net, device=0, max_batch=32, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, dtype='bf16', optimizer='adam',
                  momentum=0.0, plan_only=False, train_batch=None, dp_world=None, class_weights=None, weight_decay=0.0,
-                 label_smoothing=0.0, focal_gamma=0.0, mix=False, ema_decay=None, ema_warmup=True):
+                 label_smoothing=0.0, focal_gamma=0.0, mix=False, ema_decay=None, ema_warmup=True, distill=None):
         # dp_world: world size of the data-parallel job this replica belongs to (None: WORLD_SIZE of the launcher, else an
         # initialised torch.distributed group, else 1) -- it picks the program-lane default, and train_step_ddp checks it
         self._dp_world_arg = None if dp_world is None else int(dp_world)
@@ -233,6 +253,11 @@ class Engine:
         self.mix = bool(mix)
         if self.mix and self.focal_gamma > 0:
             raise ValueError('mix and focal_gamma do not combine: give one of them')
+        # additive (TRAIN --distill): (alpha, T) -- the train loss ops run Hinton's loss (ifcbk_softmax_xent_distill) against the logits in
+        # ``teacher_logits``, a fp32 [max_batch][NC] buffer THIS engine owns for its whole life, so plans and captured graphs hold one
+        # address; whoever runs the teacher copies its logits there ahead of a train step, on the step's stream.  None: no buffer, and
+        # plans, op tables and launches are what they were
+        self.distill = check_distill(distill, self.focal_gamma, self.mix)
         # additive (TRAIN --ema): an exponential moving average E / ERB of the parameters P and the BatchNorm running statistics RB, taken
         # inside the optimizer ops (their p[4] / p[3]) and by one ifcbk_ema_flat call per step; ema_weights() evaluates and exports it.
         # None: no shadow buffers, and plans, op tables and launches are what they were
@@ -697,6 +722,9 @@ class Engine:
             # one factor per image and input slot, 1 = unmixed; the loss ops of a slot's plans (and the graphs captured from them) hold
             # the array's address, which is why the factors live on the device and not in the ops' f[]
             self.mix_lam = [torch.ones(N, dtype=torch.float32, device=dev) for _ in range(2)]
+        if self.distill is not None:
+            # one buffer for both input slots: the teacher runs on the step's stream just ahead of the step, not in the prefetch
+            self.teacher_logits = torch.zeros(N, net.NC, dtype=torch.float32, device=dev)
         # workspace: wgrad split-K slabs / bn_bwd partials -- again over every trainable batch: the split-K depth follows the batch, and
         # resnet18's weight gradients take 12,544,000 bytes at batch 7 and 12,142,592 at batch 8 (a step at 7 on an engine of capacity
         # 8 was refused with IFCBK_ENOMEM)
@@ -1554,11 +1582,18 @@ class Engine:
         # the factors of a mixed batch (TRAIN --mixup / --cutmix) are a sixth operand of the TRAIN loss ops: p[5] != NULL sends the op to
         # ifcbk_softmax_xent_mix; the validation loss below stays the one-target loss.  Without mix the tuples are what they were
         mx = ((None,) * (1 - len(cw)) + (_vp(self.mix_lam[self.in_slot]),)) if self.mix else ()
-        lossl.add(xent, 'loss', p=(_vp(main.logits), _vp(self.target), _vp(self.loss), _vp(main.dlogits)) + cw + mx,
-                  i=(N, net.NC), f=(1.0,) + ls)
+        # a teacher's logits (TRAIN --distill) are a seventh operand of the TRAIN loss ops, with alpha and the temperature as f[3], f[4]:
+        # p[6] != NULL sends the op to ifcbk_softmax_xent_distill; both heads of inception_v3 distil from the teacher's one set of logits,
+        # and the validation loss below stays the hard loss.  Without distill the tuples are what they were
+        ds, dsf = (), ()
+        if self.distill is not None:
+            ds = (None,) * (2 - len(cw)) + (_vp(self.teacher_logits),)
+            dsf = (0.0,) * (2 - len(ls)) + self.distill
+        lossl.add(xent, 'loss', p=(_vp(main.logits), _vp(self.target), _vp(self.loss), _vp(main.dlogits)) + cw + mx + ds,
+                  i=(N, net.NC), f=(1.0,) + ls + dsf)
         for h in auxh:
-            lossl.add(xent, 'loss_aux', p=(_vp(h.logits), _vp(self.target), _vp(self.loss), _vp(h.dlogits)) + cw + mx,
-                      i=(N, net.NC), f=(0.4,) + ls, flags=1)
+            lossl.add(xent, 'loss_aux', p=(_vp(h.logits), _vp(self.target), _vp(self.loss), _vp(h.dlogits)) + cw + mx + ds,
+                      i=(N, net.NC), f=(0.4,) + ls + dsf, flags=1)
         pl.loss = Program(lossl)
         evl = OpList()
         evl.add(xent, 'val_loss', p=(_vp(main.logits), _vp(self.target), _vp(self.loss), None) + cw, i=(N, net.NC), f=(1.0,) + ls)

@@ -277,6 +277,19 @@ class FocalLoss(nn.Module):
         return (wt * (pw * li)).sum() / wt.sum()
 
 
+def check_teacher_classes(student, teacher):
+    """TRAIN --distill: the teacher's class list must be the student's, name for name and in order -- its scores are matched column by
+    column.  Raises ValueError naming the first class that differs, or the two lengths."""
+    student, teacher = list(student), list(teacher)
+    for k, (a, b) in enumerate(zip(student, teacher)):
+        if a != b:
+            raise ValueError('--distill: the teacher\'s class list differs from the training set\'s at class %d: %r (teacher) != %r'
+                             % (k, b, a))
+    if len(student) != len(teacher):
+        raise ValueError('--distill: the teacher knows %d classes, the training set has %d (the first %d agree)'
+                         % (len(teacher), len(student), min(len(student), len(teacher))))
+
+
 class NeustonModel(nn.Module):
     """``neuston_models.py:48-180`` without Lightning: same hooks, same loss, same optimizer, same
     aggregation.  ``training_step`` / ``validation_step`` / ``test_step`` accept the reference's batch tuples.
@@ -305,13 +318,22 @@ class NeustonModel(nn.Module):
         # reference hooks (training_step + a torch optimizer) write P from outside, which restarts the average
         ema = getattr(hparams, 'ema', None)
         self.ema = None if ema is None else float(ema)
+        # additive (TRAIN --distill TEACHER.ptl): the fused train loss is Hinton's, against the scores of a trained teacher that
+        # ``attach_teacher`` hands over (TRAIN does; nothing else opens the file: RUN and the ONNX export need the student alone).
+        # Absent (older files) = off.  The fused path only: ``self.criterion`` below stays the hard loss
+        ds = getattr(hparams, 'distill', None)
+        da, dt = getattr(hparams, 'distill_alpha', None), getattr(hparams, 'distill_temperature', None)
+        self.distill = None if not ds else (0.5 if da is None else float(da), 4.0 if dt is None else float(dt))
+        self.teacher = None               # a NeustonModel in inference form (attach_teacher)
+        self._teacher_ready = False       # the teacher's current input slot holds the student's current batch
         self.model = get_namebrand_model(hparams.MODEL, len(hparams.classes), hparams.pretrained, device, mb,
                                          getattr(hparams, 'precision', 'bf16') or 'bf16', optimizer=opt,
                                          lr=float(getattr(hparams, 'learning_rate', None) or 0.001),
                                          momentum=float(getattr(hparams, 'momentum', None) or 0.0), train_batch=train_batch,
                                          class_weights=cw, weight_decay=float(getattr(hparams, 'weight_decay', None) or 0.0),
                                          label_smoothing=ls, focal_gamma=fg, mix=self.mixup > 0 or self.cutmix > 0,
-                                         **({} if self.ema is None else {'ema_decay': self.ema}))
+                                         **({} if self.ema is None else {'ema_decay': self.ema}),
+                                         **({} if self.distill is None else {'distill': self.distill}))
         # what upstream would have written at neuston_models.py:55; the engine's fused loss ops compute the same weighted, smoothed mean
         eng = self.model.engine
         cwt = None if cw is None else eng.class_weight.clone()
@@ -373,6 +395,65 @@ class NeustonModel(nn.Module):
         lam, box = mix.draw(eng.net.S)
         eng.mix_batch(n, lam, box, slot=slot)
 
+    # ---- TRAIN --distill: a second model, the teacher, sees every training batch and its logits feed the student's fused loss
+    def attach_teacher(self, teacher):
+        """hand over the trained teacher (a NeustonModel, as ``load_from_checkpoint(path, device, max_batch=train batch, inference=True)``
+        returns it) of a student built with hparams ``distill``.  Any backbone and input side; its class list must be the student's."""
+        eng = self.model.engine
+        if eng.distill is None:
+            raise RuntimeError('attach_teacher: this model was built without distillation (hparams distill)')
+        check_teacher_classes(self.hparams.classes, teacher.hparams.classes)
+        teng = teacher.model.engine
+        if teng.dev != eng.dev:
+            raise ValueError('attach_teacher: the teacher lives on %s, the student on %s' % (teng.dev, eng.dev))
+        if teng.max_batch < eng.train_batch:
+            raise ValueError('attach_teacher: the teacher holds %d images, a training batch up to %d' % (teng.max_batch, eng.train_batch))
+        from .neuston_data import parse_imgnorm
+        norm = getattr(teacher.hparams, 'img_norm', None)
+        # the geometry and the normalisation the TEACHER was trained on; content and augmentation are the student's
+        self._teacher_load = dict(pad=getattr(teacher.hparams, 'pad', None))
+        if norm:
+            self._teacher_load['mean'], self._teacher_load['std'] = parse_imgnorm(norm)
+        teacher.model.eval()
+        object.__setattr__(self, 'teacher', teacher)      # not a submodule: the student's state_dict and parameters() stay its own
+        self._teacher_ready = False
+
+    def _teacher_kw(self, kw):
+        """the teacher's ``load_rois`` arguments for a batch the student loads with ``kw``: the same ROIs and per-ROI flip / turn codes,
+        resized to the teacher's S with the teacher file's img_norm and pad.  Never the jitter factors: ifcbk_roi_jitter maps ``pixels``
+        IN PLACE, so the student's load has jittered the blob by the time the teacher reads it, and a second pass would jitter it twice."""
+        out = {k: v for k, v in kw.items() if k not in ('mean', 'std', 'pad', 'jitter', 'slot')}
+        out.update(self._teacher_load)
+        return out
+
+    def _need_teacher(self):
+        if self.model.engine.distill is not None and self.teacher is None:
+            raise RuntimeError('this model trains by distillation (hparams distill) and no teacher is attached: call attach_teacher first')
+        return self.teacher is not None
+
+    def _load_teacher_batch(self, input_data):
+        """fit_batch / fit_batch_ddp: the teacher loads the batch the student just loaded, on the same (current) stream -- stream order
+        puts it behind the student's in-place jitter of the blob"""
+        teng = self.teacher.model.engine
+        if torch.is_tensor(input_data):
+            if teng.net.S != self.model.engine.net.S:
+                raise ValueError('distillation from a dense batch needs a teacher of the same input side (%d != %d): hand over ROIs'
+                                 % (teng.net.S, self.model.engine.net.S))
+            teng.load_input_nchw(input_data)
+        else:
+            teng.load_rois(**self._teacher_kw(input_data))
+        self._teacher_ready = True
+
+    def _run_teacher(self, N):
+        """the teacher's eval forward of its current batch on the current stream, and ONE device copy of its logits into the buffer the
+        student's loss ops read (``Engine.teacher_logits``, whose address the student's plans and graphs hold); no host sync"""
+        if not self._teacher_ready:
+            raise RuntimeError('distillation: the current batch was not staged for the teacher (stage_batch(..., train=True))')
+        self.teacher.model.eval()
+        self.teacher.model.engine.forward_eval(N)
+        self.model.engine.teacher_logits[:N].copy_(self.teacher.model._train_heads[0].logits[:N], non_blocking=True)
+        self._teacher_ready = False
+
     # TRAINING (fast path: one fused HIP program; loss accumulated on device, read once per epoch) #
     def fit_batch(self, input_data, input_classes):
         eng = self.model.engine
@@ -383,6 +464,9 @@ class NeustonModel(nn.Module):
         eng.target[:N].copy_(input_classes, non_blocking=True)
         if self.batch_mix is not None:
             self._mix_loaded(self.batch_mix, N)
+        if self._need_teacher():
+            self._load_teacher_batch(input_data)
+            self._run_teacher(N)
         self.model.train()
         eng.train_step(N)
         return N
@@ -390,11 +474,14 @@ class NeustonModel(nn.Module):
     # ---- pipelined form of the three batch calls: the NEXT batch is uploaded and preprocessed on a side stream into the
     # engine's other input slot while the current step runs (Engine.prefetch_begin / prefetch_end / use_prefetched):
     #     n = model.stage_batch(first);  for each batch: model.use_staged(); n2 = model.stage_batch(next); model.fit_current(n)
-    def stage_batch(self, rois, transform=None, input_classes=None):
+    def stage_batch(self, rois, transform=None, input_classes=None, train=False):
         """upload and preprocess a collated batch into the prefetch slot; jitter factors the batch carries (TRAIN --jitter) go along in
-        ``rois_to_device``'s kwargs, as they do through ``fit_batch(rois_to_device(...), ...)``"""
+        ``rois_to_device``'s kwargs, as they do through ``fit_batch(rois_to_device(...), ...)``.
+        train=True marks a TRAINING batch: with a teacher attached (TRAIN --distill) it is staged for the teacher as well, into the
+        teacher engine's own prefetch slot; validation and RUN batches are not."""
         from .neuston_data import rois_to_device
         eng = self.model.engine
+        teach = bool(train) and self._need_teacher()
         slot, side = eng.prefetch_begin()
         with torch.cuda.stream(side):
             kw = rois_to_device(rois, eng.dev, transform)
@@ -403,7 +490,25 @@ class NeustonModel(nn.Module):
                 eng.tgt_bufs[slot][:n].copy_(input_classes, non_blocking=True)
                 if getattr(transform, 'mix', None) is not None:
                     self._mix_loaded(transform.mix, n, slot=slot)       # (the training transform only carries one)
+            if teach:
+                loaded = torch.cuda.Event()
+                loaded.record(side)
         eng.prefetch_end(slot)
+        if teach:
+            # The two engines have separate prefetch streams, prefetch contexts and input slots.  Hazard 1: ifcbk_roi_jitter maps the
+            # uploaded blob in place, so it is applied once, by the student's load above, and the teacher's resize (jitter=None in
+            # _teacher_kw) waits on its own stream for the event recorded behind that load -- which also orders it behind the upload.
+            # Hazard 2: the teacher's slot is handed over by ITS prefetch_begin / prefetch_end / use_prefetched events, and
+            # use_staged() moves both engines' slots in the same call, so the teacher's slot always holds the student's batch.
+            teng = self.teacher.model.engine
+            tslot, tside = teng.prefetch_begin()
+            tside.wait_event(loaded)
+            tkw = self._teacher_kw(kw)
+            teng.load_rois(slot=tslot, **tkw)
+            for t in tkw.values():
+                if torch.is_tensor(t):
+                    t.record_stream(tside)       # allocated on the student's side stream, read on the teacher's
+            teng.prefetch_end(tslot)
         return n
 
     def stage_resident(self, res, i0, i1, transform=None):
@@ -442,9 +547,17 @@ class NeustonModel(nn.Module):
 
     def use_staged(self):
         self.model.engine.use_prefetched()
+        # (TRAIN --distill) in lockstep: a batch staged for the teacher becomes the teacher's current one in the same call
+        if self.teacher is not None:
+            teng = self.teacher.model.engine
+            self._teacher_ready = teng.prefetched is not None
+            if self._teacher_ready:
+                teng.use_prefetched()
 
     def fit_current(self, N, world=1, all_reduce=None):
         eng = self.model.engine
+        if self._need_teacher():
+            self._run_teacher(N)          # (data parallel: every rank runs the teacher on its own shard; nothing of it is communicated)
         self.model.train()
         if world > 1:
             eng.train_step_ddp(N, world, all_reduce)
@@ -492,6 +605,9 @@ class NeustonModel(nn.Module):
         eng.target[:N].copy_(input_classes, non_blocking=True)
         if self.batch_mix is not None:
             self._mix_loaded(self.batch_mix, N)
+        if self._need_teacher():
+            self._load_teacher_batch(input_data)
+            self._run_teacher(N)
         self.model.train()
         eng.train_step_ddp(N, world, all_reduce)
         return N

@@ -23,7 +23,7 @@ from torch.utils.data import DataLoader
 from .neuston_callbacks import SaveValidationResults, SaveTestResults
 from .neuston_data import (get_trainval_datasets, IfcbBinDataset, ImageDataset, IMG_EXTENSIONS, collate_rois,
                            jitter_arg, mix_alpha_arg, mix_prob_arg, pad_arg, rois_to_device)
-from .neuston_models import NeustonModel, load_checkpoint_file, load_pretrained_weights
+from .neuston_models import NeustonModel, check_teacher_classes, load_checkpoint_file, load_pretrained_weights
 
 
 def seed_everything(seed=None):
@@ -76,6 +76,20 @@ def _focal_gamma(text):
     return v
 
 
+def _distill_alpha(text):
+    v = float(text)
+    if not 0.0 <= v <= 1.0:                    # (nan fails both comparisons)
+        raise argparse.ArgumentTypeError('A must be in [0, 1], got %r' % text)
+    return v
+
+
+def _distill_temperature(text):
+    v = float(text)
+    if not 0.0 < v < float('inf'):             # (nan fails both comparisons)
+        raise argparse.ArgumentTypeError('T must be finite and > 0, got %r' % text)
+    return v
+
+
 def _ema_decay(text):
     v = float(text)
     if not 0.0 < v < 1.0:                      # (nan fails both comparisons)
@@ -84,7 +98,8 @@ def _ema_decay(text):
 
 
 class _ExclusiveLossScalar(argparse.Action):
-    """stores --label-smoothing / --focal-gamma; the second of the two to arrive non-zero is an argparse error naming both"""
+    """stores --label-smoothing / --focal-gamma (and --mixup / --cutmix / --distill); the second of the two to arrive non-zero is an
+    argparse error naming both, as is --focal-gamma, --mixup or --cutmix beside --distill"""
     FLAGS = {'label_smoothing': '--label-smoothing', 'focal_gamma': '--focal-gamma'}
 
     def __call__(self, parser, namespace, value, option_string=None):
@@ -96,6 +111,11 @@ class _ExclusiveLossScalar(argparse.Action):
             for d, flag in (('mixup', '--mixup'), ('cutmix', '--cutmix')):
                 if getattr(namespace, d, 0.0):
                     parser.error('%s and --focal-gamma do not combine: give one of them' % flag)
+        # distillation (--distill, stored through this action as well) has a loss kernel of its own, without a focal or a two-target form
+        if getattr(namespace, 'distill', None):
+            for d, flag in (('focal_gamma', '--focal-gamma'), ('mixup', '--mixup'), ('cutmix', '--cutmix')):
+                if getattr(namespace, d, 0.0):
+                    parser.error('%s and --distill do not combine: give one of them' % flag)
 
 
 def _dist():
@@ -196,9 +216,9 @@ class Trainer:
             # one batch of look-ahead: upload + on-GPU preprocessing of batch k+1 run on a side stream beside step k
             n_next = None
             for (rois, targets, paths), nxt in self._lookahead(train_loader):
-                n = model.stage_batch(rois, ttf, targets) if n_next is None else n_next
+                n = model.stage_batch(rois, ttf, targets, train=True) if n_next is None else n_next
                 model.use_staged()
-                n_next = model.stage_batch(nxt[0], ttf, nxt[1]) if nxt is not None else None
+                n_next = model.stage_batch(nxt[0], ttf, nxt[1], train=True) if nxt is not None else None
                 model.fit_current(n, self.world, self._allreduce if self.world > 1 else None)
                 global_step += 1
             model.agg_train_loss = model.epoch_train_loss()
@@ -376,6 +396,17 @@ def do_training(args):
         hi = max(range(len(args.classes)), key=lambda c: args.class_weights[c])
         print('Class-norm POWER {:g}: loss weights from {:.4g} ({}) to {:.4g} ({})'.format(
             args.class_norm, args.class_weights[lo], args.classes[lo], args.class_weights[hi], args.classes[hi]))
+    if args.distill:
+        # the teacher's class list is checked from its file's hyper-parameters alone, before anything is built or trained
+        thp = load_checkpoint_file(args.distill)['hyper_parameters']
+        try:
+            check_teacher_classes(args.classes, thp['classes'])
+        except ValueError as e:
+            raise SystemExit('TRAIN {}'.format(e))
+        args.distill_teacher_id = thp.get('model_id')
+    else:
+        # unset: the model file and args.yml carry no distillation entry at all
+        del args.distill, args.distill_alpha, args.distill_temperature
     dist, rank, world = _dist()
     if rank == 0:
         with open(os.path.join(args.outdir, 'training_images.list'), 'w') as f:
@@ -400,6 +431,16 @@ def do_training(args):
         loaded, skipped = load_pretrained_weights(classifier.model, args.weights)
         print('Loaded {} pretrained tensors from {}; freshly initialised: {}'.format(
             len(loaded), args.weights, [k for k in skipped if not k.endswith('num_batches_tracked')]))
+    if getattr(args, 'distill', None):
+        # loaded as RUN loads a model: activations for a training batch, gradient-side buffers for one image
+        teacher = NeustonModel.load_from_checkpoint(args.distill, device=int(os.environ.get('LOCAL_RANK', 0)),
+                                                    max_batch=args.batch_size, inference=True)
+        if teacher.model.engine.max_batch < args.batch_size:
+            raise SystemExit('TRAIN --distill: the teacher ({}) holds {} images per program, --batch is {}'.format(
+                teacher.hparams.MODEL, teacher.model.engine.max_batch, args.batch_size))
+        classifier.attach_teacher(teacher)
+        print('Distilling from {} ({}, {} classes): alpha {:g}, temperature {:g}'.format(
+            args.distill, teacher.hparams.MODEL, len(teacher.hparams.classes), args.distill_alpha, args.distill_temperature))
     eng = classifier.model.engine
     if eng.window_batch < args.batch_size:
         # --batch is per GPU as upstream (neuston_net.py:102); BatchNorm statistics are per step, so a step cannot be chunked
@@ -625,6 +666,9 @@ def argparse_nn_train(train_subparser):
     optim.add_argument('--label-smoothing', metavar='EPS', default=0.0, type=_label_smoothing, action=_ExclusiveLossScalar, help='Label smoothing of the loss, as nn.CrossEntropyLoss(label_smoothing=EPS): the target distribution is (1-EPS) one-hot + EPS/C uniform, for noisy annotations. A float in [0, 1]; val_loss follows the smoothed value. Default is 0 (hard labels)')
     optim.add_argument('--focal-gamma', metavar='GAMMA', default=0.0, type=_focal_gamma, action=_ExclusiveLossScalar, help='Focal loss against class imbalance: the loss of an image is scaled by (1 - p)^GAMMA, p the softmax probability of its class, so images the network already classifies confidently count less. A finite float >= 0; composes with --class-norm (its weights are the per-class alpha), not with --label-smoothing; val_loss follows the focal value. Default is 0 (cross-entropy)')
     optim.add_argument('--ema', metavar='DECAY', type=_ema_decay, default=None, help='(MI355X path, additive) Keep an exponential moving average of the weights and of the BatchNorm running statistics, updated inside the fused optimizer step: avg += (1 - d) * (weights - avg) after every step, d = min(DECAY, (1 + t) / (10 + t)) at the t-th step (the warm-up of TensorFlow\'s ExponentialMovingAverage), as torch.optim.swa_utils.get_ema_multi_avg_fn / timm\'s ModelEmaV3. Validation (val_loss, F1, --results files), early stopping, the choice of the best epoch, the saved model and --onnx then use the averaged weights; the training trajectory is unchanged. A float in (0, 1), e.g. 0.999. Default (unset) is no averaging')
+    optim.add_argument('--distill', metavar='TEACHER.ptl', default=None, action=_ExclusiveLossScalar, help='(MI355X path, additive) Knowledge distillation: train MODEL to match the class scores of a trained teacher model file as well as the labels, (1 - A) * CrossEntropy + A * T^2 * KL(softmax(teacher / T) || softmax(student / T)). The teacher may be any backbone and input size (e.g. an inception_v3 teacher for a resnet18 student); its class list must equal the training set\'s. It sees every training batch with the same flips, turns and jitter, resized and normalised as it was trained. Composes with --class-norm (hard term only) and --label-smoothing, not with --focal-gamma, --mixup or --cutmix; val_loss stays the hard loss. RUN needs the student file alone. Default (unset) is no teacher')
+    optim.add_argument('--distill-alpha', metavar='A', type=_distill_alpha, default=0.5, help='Weight of the teacher term of --distill, a float in [0, 1]. Default is 0.5')
+    optim.add_argument('--distill-temperature', metavar='T', type=_distill_temperature, default=4.0, help='Softmax temperature of --distill, a finite float > 0. Default is 4')
     meta = t.add_argument_group(title='Metadata and Annotations')
     meta.add_argument('--dataset-id', help='Associate a dataset id label with this model')
     meta.add_argument('--notes', help='Add any kind of note to the trained model.')

@@ -267,6 +267,23 @@ IFCBK_API int ifcbk_softmax_xent_focal(ifcbk_ctx*, const float* logits, const in
 IFCBK_API int ifcbk_softmax_xent_mix(ifcbk_ctx*, const float* logits, const int64_t* target, const float* lam /*[N]*/,
                            const float* class_weight /*nullable*/, int N, int NC, float weight, float label_smoothing, float* loss_out,
                            int loss_accumulate, float* dlogits /*nullable*/, void* stream);
+/* knowledge distillation (TRAIN --distill) on the same operands: Hinton's loss against a teacher's logits.  a = weight, T = temperature,
+ * r = softmax(logits / T), q = softmax(teacher / T), H and Dh = loss and dlogits of ifcbk_softmax_xent_ls at weight 1 (the same
+ * class_weight, label_smoothing and normaliser W); class weights act on the hard term only:
+ * K = 1 / N * sum_i sum_j q_i[j] (log q_i[j] - log r_i[j])                                   (KL(q || r), "batchmean");
+ * loss_out[0] (+)= a * ((1 - alpha) * H + alpha * T^2 * K);
+ * dlogits_i[j] = a * ((1 - alpha) * Dh_i[j] + alpha * T / N * (r_i[j] - q_i[j])),
+ * i.e. (1 - alpha) CrossEntropyLoss(weight, label_smoothing)(s, y) + alpha T^2 F.kl_div(log_softmax(s / T), softmax(z / T), 'batchmean').
+ * x / T is a correctly rounded division of the rounded x - max; log q - log r is formed from those arguments and the logs of the two
+ * sums, never from a stored probability: a q that underflows to 0 adds exactly 0 to the loss and leaves a * alpha * T / N * r in
+ * dlogits.  alpha = 0 is ifcbk_softmax_xent_ls's function (not its bits) and reads teacher without using it; alpha = 1 multiplies the
+ * hard term by an exact 0: without class weights the result does not depend on target.  teacher: [N][NC] fp32 logits on the device.
+ * IFCBK_EINVAL: NULL logits / target / teacher / loss_out, N or NC < 1, alpha outside [0, 1] or NaN, temperature not finite or <= 0,
+ * label_smoothing outside [0, 1]; a target outside [0, NC) and W == 0 are the caller's fault, as above.  One block, fixed summation
+ * order: bitwise reproducible.                                                                                                       */
+IFCBK_API int ifcbk_softmax_xent_distill(ifcbk_ctx*, const float* logits, const int64_t* target, const float* teacher /*[N][NC]*/,
+                               const float* class_weight /*nullable*/, int N, int NC, float weight, float label_smoothing, float alpha,
+                               float temperature, float* loss_out, int loss_accumulate, float* dlogits /*nullable*/, void* stream);
 /* the bookkeeping of one fused train step, in the step's own op table (no framework kernel between the first and the last
  * launch of a step): num_batches_tracked[0..n) += 1 of every BatchNorm ([PL]/torch: nn.BatchNorm2d.forward in training) and
  * loss_sum += loss (the reference's train_loss is the SUM of the batch losses, neuston_models.py:85).  Either part may be NULL. */
@@ -502,7 +519,11 @@ enum {
                               * ifcbk_softmax_xent_focal with the same operands; f[1] != 0 together with f[2] != 0 is IFCBK_EINVAL.
                               * p[5] = the factors of a mixed batch (float[N], device), for the same two kinds: NULL, what a zeroed op
                               * holds, is the dispatch above; an array runs ifcbk_softmax_xent_mix with the same operands and f[1] as its
-                              * label smoothing; an array together with f[2] != 0 is IFCBK_EINVAL                                       */
+                              * label smoothing; an array together with f[2] != 0 is IFCBK_EINVAL.
+                              * p[6] = a teacher's logits (float[N][NC], device), f[3] = alpha, f[4] = temperature, for the same two kinds:
+                              * NULL, what a zeroed op holds, is the dispatch above; an array runs ifcbk_softmax_xent_distill with the
+                              * same operands, f[1] as its label smoothing and p[4] as its class weights (NULL for the plain kind); an
+                              * array together with f[2] != 0 or with p[5] is IFCBK_EINVAL                                              */
 };
 typedef struct {
     ifcbk_conv_desc d;
