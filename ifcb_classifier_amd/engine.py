@@ -14,6 +14,7 @@ import torch
 
 from . import _lib
 from ._lib import Op, ConvDesc, BnDesc, PoolDesc, HeadDesc, RoiDesc, pad_fill
+from .plan import OpList, Program, PlanBuilder, schedule_lanes, _overlap, _vp       # noqa: F401  (re-exported: tests import them from here)
 
 
 # environment switches the library reads at launch time that change a workspace size or a partial-row count (csrc/conv_*.hip,
@@ -32,10 +33,6 @@ def dtype_is_bf16(eng):
     return eng.dtype == 'bf16'
 
 
-def _vp(t, byte_off=0):
-    return None if t is None else C.c_void_p(t.data_ptr() + byte_off)
-
-
 def ema_decay_at(decay, t, warmup=True):
     """decay of the t-th update (t = 1, 2, ...) of a weight average since it was initialised: min(decay, (1 + t) / (10 + t)), the
     warm-up of TensorFlow's ExponentialMovingAverage(num_updates) -- a short training is not held to its initial weights for
@@ -46,130 +43,6 @@ def ema_decay_at(decay, t, warmup=True):
 def ema_weight(decay, t, warmup=True):
     """the w of e <- e + w (p - e) for that update: 1 - d_t in double, rounded ONCE to fp32 (what the kernels are given)"""
     return C.c_float(1.0 - ema_decay_at(decay, t, warmup)).value
-
-
-class OpList:
-    """ops + tags + scheduling metadata: (lane, reads, writes) per op.  A resource is (key..., lo, hi): a channel range
-    of a tensor.  An op without annotations is a full barrier on lane 0 (loss, head, Adam, pack ...)."""
-
-    def __init__(self):
-        self.ops = []
-        self.tags = []
-        self.meta = []
-
-    def add(self, kind, tag, p=(), i=(), f=(), flags=0, conv=None, bn=None, pool=None, head=None, lane=0, reads=None,
-            writes=None):
-        o = Op()
-        o.kind, o.flags = kind, flags
-        self.meta.append((lane, reads, writes))
-        for k, v in enumerate(p):
-            o.p[k] = v if (v is None or isinstance(v, int)) else v.value
-        for k, v in enumerate(i):
-            o.i[k] = int(v)
-        for k, v in enumerate(f):
-            o.f[k] = float(v)
-        if conv is not None:
-            o.u.conv = conv
-        elif bn is not None:
-            o.u.bn = bn
-        elif pool is not None:
-            o.u.pool = pool
-        elif head is not None:
-            o.u.head = head
-        self.ops.append(o)
-        self.tags.append(tag)
-        return o
-
-    def extend(self, other):
-        self.ops.extend(other.ops)
-        self.tags.extend(other.tags)
-        self.meta.extend(other.meta)
-
-    def slice(self, b0, b1):
-        sub = OpList()
-        sub.ops, sub.tags, sub.meta = self.ops[b0:b1], self.tags[b0:b1], self.meta[b0:b1]
-        return sub
-
-    def freeze(self):
-        arr = (Op * len(self.ops))(*self.ops)
-        for k, (lane, wait) in enumerate(schedule_lanes(self.meta)):
-            arr[k].flags = (arr[k].flags & 0xff) | (lane << 8) | (wait << 12)
-        return arr
-
-
-def _overlap(a, b):
-    return a[:-2] == b[:-2] and a[-2] < b[-1] and b[-2] < a[-1]
-
-
-def schedule_lanes(meta):
-    """(lane, wait mask) per op from the static data flow: an op waits for the lanes that hold an unfinished producer of
-    something it reads, or an unfinished reader / writer of something it writes.  A wait covers everything queued on the
-    waited lane so far (and, transitively, whatever that lane had waited for), which is remembered to skip redundant waits."""
-    NL = 8
-    count = [0] * NL                              # ops queued per lane
-    synced = [[0] * NL for _ in range(NL)]        # synced[L][j]: lane L is ordered after the first synced[L][j] ops of lane j
-    table = {}                                    # resource -> [writer (lane, pos) or None, readers [(lane, pos)]]
-    star = ('*', 0, 1)
-    out = []
-    for lane, reads, writes in meta:
-        if reads is None and writes is None:
-            lane, reads, writes = 0, [star], [star]           # barrier
-        else:
-            reads, writes = list(reads or ()) + [star], list(writes or ())
-        deps = set()
-        for r in reads:
-            for res, (w, _rd) in table.items():
-                if w is not None and _overlap(r, res):
-                    deps.add(w)
-        for wres in writes:
-            for res, (w, rd) in table.items():
-                if _overlap(wres, res):
-                    if w is not None:
-                        deps.add(w)
-                    deps.update(rd)
-        wait = 0
-        for (lj, pj) in deps:
-            if lj != lane and pj >= synced[lane][lj]:
-                wait |= 1 << lj
-        for lj in range(NL):
-            if wait >> lj & 1:
-                synced[lane][lj] = count[lj]
-                for k in range(NL):
-                    if k != lane:
-                        synced[lane][k] = max(synced[lane][k], synced[lj][k])
-        me = (lane, count[lane])
-        count[lane] += 1
-        for r in reads:
-            table.setdefault(r, [None, []])[1].append(me)
-        for wres in writes:
-            for res in [res for res in table if _overlap(wres, res)]:
-                table[res] = [me, []]
-            table[wres] = [me, []]
-        out.append((lane, wait))
-    return out
-
-
-class Program:
-    def __init__(self, oplist):
-        self.tags = list(oplist.tags)
-        self.n = len(oplist.ops)
-        self.arr = oplist.freeze()
-        self.lanes = sorted({m[0] for m in oplist.meta if not (m[1] is None and m[2] is None)} | {0})
-
-    def find(self, kind):
-        return [k for k in range(self.n) if self.arr[k].kind == kind]
-
-    def timed(self, which=None, single_lane=False):
-        """a copy of the op table in which the ops `which` (indices; None = all) carry flags bit 7: ifcbk_run_program_ev
-        brackets exactly those with HIP events.  single_lane: drop the lane / wait bits, i.e. run every op back to back
-        on the caller's stream (per-kernel durations without another lane's kernel sharing the GPU)"""
-        arr = (Op * self.n)(*self.arr)
-        for k in (range(self.n) if which is None else which):
-            arr[k].flags |= 0x80
-        if single_lane:
-            for k in range(self.n):
-                arr[k].flags &= 0xff
-        return arr
 
 
 # The largest activation an engine may hold: that of the largest batch an eval program was verified on, bit for bit against its
@@ -674,6 +547,10 @@ class Engine:
         self.draw = [torch.zeros(Nt * max_raw, dtype=bf, device=dev) for _ in range(self.NL)]
         gmax = max([g.x.H * g.x.W * g.Ktot for g in self.groups] + [0])
         self.draw_group = torch.zeros(max(1, Nt * gmax), dtype=bf, device=dev)
+        # ... and the d(raw) tensors that outlive their layer's backward (own_draw / group_draw), out of one pool (_carve)
+        self.draw_own, self._draw_pool, self._draw_used = {}, None, 0
+        for g in self.groups:
+            g.draw_own = None
         # partial BatchNorm sums, per lane: rows x 2 x channels of the largest layer -- over EVERY batch a plan can be built for, not
         # the capacity alone.  The row count follows the kernel the library picks for a batch, so it is not monotonic: resnet18 takes
         # 125,440 floats at batch 5 and 100,352 at batch 8, and the partial last batch of an epoch runs on these buffers
@@ -730,12 +607,44 @@ class Engine:
         # 8 was refused with IFCBK_ENOMEM)
         self.ctx.reserve(max([1 << 20] + [self._train_workspace(b) for b in range(1, Nt + 1)]))
 
+    def _carve(self, nelem):
+        """a d(raw) buffer out of ONE pooled allocation per engine (78 tensors of an inception plan: one hipMalloc instead of 78,
+        not zero-filled -- BatchNorm backward writes every element before anything reads it)"""
+        if not self.wgrad_lane:
+            # (without a weight-gradient lane only the members of grouped launches keep a buffer of their own: a handful of
+            # tensors -- a pool sized for EVERY conv, 4.6 GB at batch 256, would be mostly unused)
+            return torch.empty(nelem, dtype=self.tdtype, device=self.dev)
+        if self._draw_pool is None:
+            own = [m.P * m.Q * m.K for m in self.convs if m.group is None or m.cpool is not None]
+            tot = sum((self.train_batch * per_img + 127) // 128 * 128 for per_img in own + [g.x.H * g.x.W * g.Ktot for g in self.groups])
+            self._draw_pool = torch.empty(max(tot, 128), dtype=self.tdtype, device=self.dev)
+        n = (nelem + 127) // 128 * 128
+        if self._draw_used + n > self._draw_pool.numel():
+            return torch.empty(nelem, dtype=self.tdtype, device=self.dev)
+        v = self._draw_pool[self._draw_used:self._draw_used + nelem]
+        self._draw_used += n
+        return v
+
+    def own_draw(self, m):
+        """conv m's d(raw) in a buffer of its own, kept for the engine's life (carved on first use: the order is the plan builder's)"""
+        if m not in self.draw_own:
+            self.draw_own[m] = self._carve(self.train_batch * m.P * m.Q * m.K)
+        return self.draw_own[m]
+
+    def group_draw(self, g):
+        """the merged d(raw) tensor of a sibling GEMM: the shared scratch, or the group's own when weight gradients have a lane"""
+        if not self.wgrad_lane:
+            return self.draw_group
+        if g.draw_own is None:
+            g.draw_own = self._carve(self.train_batch * g.x.H * g.x.W * g.Ktot)
+        return g.draw_own
+
     def _plan_batches(self):
         """every batch whose plan touches the training-side scratch (1 .. train_batch), and the capacity"""
         return list(range(1, self.train_batch + 1)) + ([self.max_batch] if self.max_batch > self.train_batch else [])
 
     def _bn_part_floats(self, N):
-        """floats one lane's partial-sum buffer must hold for a plan at batch N (every producer of partial rows in _build)"""
+        """floats one lane's partial-sum buffer must hold for a plan at batch N (every producer of partial rows in plan.PlanBuilder)"""
         lib = self.ctx.lib
         need = [16]
         for n in self.convs:
@@ -894,7 +803,7 @@ class Engine:
             raise RuntimeError('batch %d exceeds the engine capacity %d' % (N, self.max_batch))
         key = (N, self.in_slot, self.in_kind[self.in_slot])
         if key not in self._plans:
-            self._plans[key] = self._build(N)
+            self._plans[key] = PlanBuilder(self, N).build()
             self._plans[key].dispatch_env = _dispatch_env()
         pl = self._plans[key]
         if pl.dispatch_env != _dispatch_env():
@@ -903,837 +812,6 @@ class Engine:
             raise RuntimeError('a kernel-dispatch switch (%s) changed after the plan for batch %d was built: build a new model/engine '
                                'instead' % (', '.join(k for k, v in zip(_DISPATCH_SWITCHES, pl.dispatch_env) if os.environ.get(k) != v), N))
         return pl
-
-    def _build(self, N):
-        net = self.net
-        fwd_t, fwd_e, bwd = OpList(), OpList(), OpList()
-        pack, evalprep = OpList(), OpList()
-        written = set()       # grad buffers already written in this backward pass
-
-        def acc_flag(buf):
-            a = 1 if buf.id in written else 0
-            written.add(buf.id)
-            return a
-
-        # conv -> BN -> ReLU whose activation feeds ONLY a 3x3/stride-2 max pool (inception Conv2d_2b / Conv2d_4a, the
-        # resnet stem): in training the activation and its gradient are never materialised (bn_apply_maxpool / bn_bwd_maxpool)
-        readers = {}
-        for m in net.nodes:
-            for v in ((m.x, getattr(m, 'residual', None)) if m.kind == 'conv' else (m.x,)):
-                if v is not None:
-                    readers.setdefault(v.buf.id, []).append(m)
-        pool_cand = {}        # conv node -> (pool node, its index): the candidates, whatever the switches say
-        for kk, m in enumerate(net.nodes):
-            if (m.kind == 'max' and m.R == 3 and m.S == 3 and m.sh == 2 and m.sw == 2 and m.ph <= 1 and m.pw <= 1
-                    and m.x.is_full and len(readers.get(m.x.buf.id, ())) == 1):
-                prod = [c for c in net.nodes if c.kind == 'conv' and c.y.buf.id == m.x.buf.id]
-                if (len(prod) == 1 and prod[0].y.is_full and prod[0].relu and prod[0].residual is None
-                        and prod[0].group is None and bool(prod[0].aux) == bool(m.aux)):
-                    pool_cand[prod[0]] = (m, kk)
-        # IFCBK_FUSE_POOL: the TRAINING fusion (bn_apply_maxpool / bn_bwd_maxpool); IFCBK_FUSE_POOL_EVAL: the eval one below --
-        # two switches, two decisions
-        fused_pool = dict(pool_cand) if os.environ.get('IFCBK_FUSE_POOL', '1') != '0' else {}
-        fused_pool_nodes = {v[0] for v in fused_pool.values()}
-        self.fused_pool = fused_pool
-        # eval twin: conv + folded BatchNorm + ReLU + that max pool in ONE kernel where the row-streaming conv serves the layer
-        # (inception Conv2d_2b -> maxpool1): the 708 MB activation of a batch of 256 is neither written nor read back
-        fused_pool_eval = {}
-        if os.environ.get('IFCBK_FUSE_POOL_EVAL', '1') != '0' and not self.plan_only:
-            for cn, (pn, pk) in pool_cand.items():
-                if (pn.ph == 0 and pn.pw == 0 and cn.y.buf.C == cn.K
-                        and self.ctx.lib.ifcbk_conv2d_fwd_affine_maxpool_ok(C.byref(self._conv_desc(cn, N)))):
-                    fused_pool_eval[cn] = pn
-        fused_pool_eval_nodes = set(fused_pool_eval.values())
-        # conv c whose input is the private BN+ReLU activation of conv n: c's input-gradient kernel also reduces n's BN
-        # backward sums in its epilogue (ifcbk_conv2d_dgrad_bnstat) and n's BN backward skips its reduction pass
-        bnstat_of = {}        # consumer conv -> producer conv
-        # IFCBK_FUSE_BNSTAT: 1 (default) fuses, 0 is the unfused reference the parity tests compare against
-        fuse_bnstat = os.environ.get('IFCBK_FUSE_BNSTAT', '1')
-        if fuse_bnstat not in ('0', '1'):
-            raise ValueError('IFCBK_FUSE_BNSTAT must be 0 or 1, got %r' % fuse_bnstat)
-        keep = []             # host tables the op tables point into
-        if fuse_bnstat == '1':
-            for cnode in net.nodes:
-                if cnode.kind != 'conv' or cnode.group is not None or cnode.x.buf.is_input or not cnode.x.is_full:
-                    continue
-                if len(readers.get(cnode.x.buf.id, ())) != 1:
-                    continue
-                prod = [c for c in net.nodes if c.kind == 'conv' and c.y.buf.id == cnode.x.buf.id]
-                if (len(prod) == 1 and prod[0].y.is_full and prod[0].relu and prod[0].residual is None
-                        and prod[0] not in fused_pool and bool(prod[0].aux) == bool(cnode.aux)
-                        and self._conv_desc(cnode, N).C == cnode.x.C      # not the flattened full-cover form: its 'channels' are (tap, c)
-                        and self.ctx.lib.ifcbk_conv2d_dgrad_bnstat_mblocks(C.byref(self._conv_desc(cnode, N))) > 0):
-                    bnstat_of[cnode] = prod[0]
-        bnstat_done = {}      # producer conv -> (partials pointer, row count, resource of the partial buffer)
-
-        # ---- lanes: every chain of nodes that hangs off a shared tensor (an Inception block input, a resnet block
-        # input) gets a lane, round-robin; a node fed by a private tensor stays on its producer's lane
-        NL = self.NL
-        producers = {}
-        for m in net.nodes:
-            if m.kind != 'head':
-                producers.setdefault(m.y.buf.id, []).append(m)
-
-        # Which chain gets which lane: chains in order of appearance -- lane 0 (the caller's stream, where the sibling GEMMs and their
-        # gradients run) takes the light 1x1 branch, the heavy chains land on lanes 1 and 2.  Putting the HEAVIEST chain of every
-        # block on lane 0 (round 2) or rotating the lanes so that a block's GEMM follows the previous block's heaviest chain on the
-        # same stream (round 3) both lose ~1 ms per step: the event wait they save is cheaper than what they serialise.
-
-        def follows_of():
-            f = {}
-            for m in net.nodes:
-                if m.aux or m.kind == 'head':
-                    continue
-                prods = producers.get(m.x.buf.id, [])
-                if (len(prods) == 1 and prods[0].y.is_full and m.x.is_full and len(readers.get(m.x.buf.id, ())) == 1
-                        and not prods[0].aux):
-                    f[m] = prods[0]
-            return f
-
-        def assign_lanes(nl):
-            follows = follows_of()
-            head_of = {}
-            for m in net.nodes:                       # forward order: a follower's producer is already resolved
-                if m.aux or m.kind == 'head':
-                    continue
-                head_of[m] = head_of[follows[m]] if m in follows and follows[m] in head_of else m
-            by_tensor = {}
-            for m in net.nodes:
-                if not m.aux and m.kind != 'head' and head_of.get(m) is m:
-                    by_tensor.setdefault(m.x.buf.id, []).append(m)
-            rank = {}
-            for heads in by_tensor.values():
-                for k, h in enumerate(heads):
-                    rank[h] = k
-            lanes = {}
-            for m in net.nodes:
-                if m.aux:
-                    lanes[m] = 1 % nl     # the auxiliary classifier (pool, 2 convs, fc) runs beside Mixed_7a..7c
-                elif m.kind == 'head':
-                    lanes[m] = 0
-                else:
-                    lanes[m] = rank[head_of[m]] % nl
-            return lanes
-
-        # training and eval programs get their own lane counts: measured (B=256) 2 / 3 / 4 lanes = 25.9 / 25.5 / 25.3 ms per
-        # train step but 6.12 / 6.63 / 6.78 ms per eval forward (its kernels are few and wide: more lanes only add waits)
-        WLs = list(range(NL - self.wgrad_lane, NL))        # the weight-gradient lanes
-        wl_next = [0]
-        lane_of = assign_lanes(NL - self.wgrad_lane)
-        lane_eval = assign_lanes(self.NL_eval)
-        if not hasattr(self, 'draw_own'):
-            self.draw_own = {}
-
-        def _carve(nelem):
-            """a d(raw) buffer out of ONE pooled allocation per engine (78 tensors of an inception plan: one hipMalloc instead of 78,
-            not zero-filled -- BatchNorm backward writes every element before anything reads it)"""
-            if not self.wgrad_lane:
-                # (without a weight-gradient lane only the members of grouped launches keep a buffer of their own: a handful of
-                # tensors -- a pool sized for EVERY conv, 4.6 GB at batch 256, would be mostly unused)
-                return torch.empty(nelem, dtype=self.tdtype, device=self.dev)
-            if getattr(self, '_draw_pool', None) is None:
-                tot = 0
-                for m in self.convs:
-                    if m.group is None or m.cpool is not None:
-                        tot += (self.train_batch * m.P * m.Q * m.K + 127) // 128 * 128
-                for gq in self.groups:
-                    tot += (self.train_batch * gq.x.H * gq.x.W * gq.Ktot + 127) // 128 * 128
-                self._draw_pool = torch.empty(max(tot, 128), dtype=self.tdtype, device=self.dev)
-                self._draw_used = 0
-            n = (nelem + 127) // 128 * 128
-            if self._draw_used + n > self._draw_pool.numel():
-                return torch.empty(nelem, dtype=self.tdtype, device=self.dev)
-            v = self._draw_pool[self._draw_used:self._draw_used + nelem]
-            self._draw_used += n
-            return v
-
-        def own_draw(m):
-            if m not in self.draw_own:
-                self.draw_own[m] = _carve(self.train_batch * m.P * m.Q * m.K)
-            return self.draw_own[m]
-
-        def group_draw(gq):
-            """the merged d(raw) tensor of a sibling GEMM: the shared scratch, or the group's own when weight gradients have a lane"""
-            if not self.wgrad_lane:
-                return self.draw_group
-            if getattr(gq, 'draw_own', None) is None:
-                gq.draw_own = _carve(self.train_batch * gq.x.H * gq.x.W * gq.Ktot)
-            return gq.draw_own
-
-        # ---- resources for the lane scheduler: channel ranges of tensors
-        def ra(v):
-            return ('a', v.buf.id, v.coff, v.coff + v.C)
-
-        def rg(v):
-            return ('g', v.buf.id, v.coff, v.coff + v.C)
-
-        def rraw(m):
-            if m.group is not None and m.cpool is None:
-                return ('gr', id(m.group), m.koff, m.koff + m.K)
-            return ('r', m.raw.id, 0, m.K)
-
-        absorbed = self.absorbed_pools
-
-        def rdg(m):
-            return ('dg', id(m.group), m.koff, m.koff + m.K)
-
-        rst = lambda m: ('s', id(m), 0, 1)
-        rbp = lambda L: ('bp', L, 0, 1)
-        ram = lambda kk: ('am', kk, 0, 1)
-
-        bwd_groups = []
-        for k, n in enumerate(net.nodes):
-            grp = OpList()
-            L = lane_of[n]
-            if n.kind == 'conv':
-                M = N * n.P * n.Q
-                d = self._conv_desc(n, N)
-                # forward conv writes the raw output (own buffer, ld = K)
-                raw, ldraw = self._raw_ptr(n)
-                dfw = ConvDesc.from_buffer_copy(d)
-                dfw.ldy = ldraw
-                wk = _vp(self.Wsh, self.esize * n.w_off)
-                wT = _vp(self.Wsh, self.esize * n.wT_off)
-                ckey, bkey = n.conv_key + '.weight', n.bn_key
-                mb = self.ctx.lib.ifcbk_conv2d_fwd_mblocks(C.byref(d))
-                # the stem conv on the resized u8 plane of this slot (conv_stem_u8.hip) instead of the [N,S,S,8] tensor
-                u8 = self.stem_u8 is n and self.in_kind[self.in_slot] == 'u8'
-                if u8:
-                    mb = self.ctx.lib.ifcbk_stem_u8_rows(C.byref(d))
-                    gu8, gab = _vp(self.in_u8[self.in_slot]), _vp(self.in_ab[self.in_slot])
-                bnd = BnDesc(M, n.K, ldraw, n.y.buf.C, 1 if n.relu else 0, self.cdtype, n.eps, 0.1)
-                g = n.group
-                first_of_group = g is not None and g.members[0] is n
-                res = self._aptr(n.residual) if n.residual is not None else None
-                ldr = n.residual.buf.C if n.residual is not None else 0
-                for lst, train in ((fwd_t, True), (fwd_e, False)):
-                    if n.aux and not train:
-                        continue
-                    Le = lane_eval[n]
-                    if not train and g is not None and self.eval_groups:
-                        # inference: the sibling 1x1 convs of a block as ONE GEMM with per-segment destinations
-                        # (ifcbk_conv2d_fwd_affine_segments): members with their folded BatchNorm + ReLU straight into their output
-                        # tensors, a commuted pool branch raw into its slice of the sibling tensor (its pool applies the affine)
-                        if first_of_group:
-                            gd = self._group_desc(g, N)
-                            ys, iv, wr = [], [], []
-                            for m in g.members:
-                                if m.cpool is not None:
-                                    pre, ldpre = self._pre_ptr(m)
-                                    ys.append(pre); iv.append(m.K | (ldpre << 20)); wr.append(('gr', id(g), m.koff, m.koff + m.K))
-                                else:
-                                    ys.append(self._aptr(m.y)); iv.append(m.K | (m.y.buf.C << 20) | (1 << 40)); wr.append(ra(m.y))
-                            ys += [None] * (4 - len(ys))
-                            iv += [0] * (4 - len(iv))
-                            lst.add(_lib.OP_CONV_FWD_AFFINE_SEG, '+'.join(m.name for m in g.members),
-                                    p=(self._aptr(g.x), _vp(self.Wsh, self.esize * g.w_off), ys[0], ys[1], ys[2], ys[3],
-                                       self._stat(g.members[0], 4), self._stat(g.members[0], 5)),
-                                    i=iv, conv=gd, lane=Le, reads=[ra(g.x)], writes=wr)
-                        if n.cpool is not None:
-                            cp = n.cpool
-                            pre, ldpre = self._pre_ptr(n)
-                            ppd = PoolDesc(N, cp.x.H, cp.x.W, n.K, ldpre, 3, 3, 1, 1, 1, 1, cp.P, cp.Q, n.y.buf.C, self.cdtype)
-                            lst.add(_lib.OP_AVGPOOL_AFFINE, cp.name + '(' + n.name + ')',
-                                    p=(pre, self._stat(n, 4), self._stat(n, 5), self._aptr(n.y)), flags=4 if n.relu else 0, pool=ppd,
-                                    lane=Le, reads=[('gr', id(g), n.koff, n.koff + n.K)], writes=[ra(n.y)])
-                        continue
-                    if not train and n.cpool is not None:
-                        # inference twin of the commuted pool branch: plain 1x1 conv of the block input into the branch's slice of
-                        # the sibling tensor, then avgpool with the eval-BN affine + ReLU in its epilogue
-                        cp = n.cpool
-                        pre, ldpre = self._pre_ptr(n)
-                        dpre = ConvDesc(N, cp.x.H, cp.x.W, cp.x.C, cp.x.buf.C, n.K, 1, 1, 1, 1, 0, 0, n.P, n.Q, ldpre, n.Cw, self.cdtype)
-                        rpre = ('gr', id(g), n.koff, n.koff + n.K)
-                        lst.add(_lib.OP_CONV_FWD, n.name, p=(self._aptr(cp.x), wk, pre, None), conv=dpre, lane=Le,
-                                reads=[ra(cp.x)], writes=[rpre])
-                        ppd = PoolDesc(N, cp.x.H, cp.x.W, n.K, ldpre, 3, 3, 1, 1, 1, 1, cp.P, cp.Q, n.y.buf.C, self.cdtype)
-                        lst.add(_lib.OP_AVGPOOL_AFFINE, cp.name + '(' + n.name + ')',
-                                p=(pre, self._stat(n, 4), self._stat(n, 5), self._aptr(n.y)), flags=4 if n.relu else 0, pool=ppd,
-                                lane=Le, reads=[rpre], writes=[ra(n.y)])
-                        continue
-                    if not train and u8:
-                        lst.add(_lib.OP_STEM_U8_FWD, n.name,
-                                p=(gu8, self._pptr(ckey), gab, self._aptr(n.y), None, self._stat(n, 4), self._stat(n, 5)),
-                                flags=4 if n.relu else 0, conv=d, lane=Le, reads=[ra(n.x)], writes=[ra(n.y)])
-                        continue
-                    if not train and n in fused_pool_eval:
-                        pn = fused_pool_eval[n]
-                        lst.add(_lib.OP_CONV_FWD_AFFINE_MAXPOOL, n.name + '+' + pn.name,
-                                p=(self._aptr(n.x), wk, self._aptr(pn.y), self._stat(n, 4), self._stat(n, 5)),
-                                i=(pn.y.buf.C,), flags=4 if n.relu else 0, conv=d, lane=Le, reads=[ra(n.x)], writes=[ra(pn.y)])
-                        continue
-                    if not train:
-                        # inference: eval-BN affine (+residual) + ReLU fused into the conv epilogue; no raw tensor
-                        lst.add(_lib.OP_CONV_FWD_AFFINE, n.name,
-                                p=(self._aptr(n.x), wk, self._aptr(n.y), self._stat(n, 4), self._stat(n, 5), res),
-                                i=(ldr,), flags=4 if n.relu else 0, conv=d, lane=Le,
-                                reads=[ra(n.x)] + ([ra(n.residual)] if n.residual is not None else []), writes=[ra(n.y)])
-                        continue
-                    if g is not None:
-                        if not first_of_group:
-                            continue                      # emitted with the group's first member
-                        # ONE GEMM for all sibling 1x1 convs, then each branch's BN on its channel slice
-                        gd = self._group_desc(g, N)
-                        gmb = self.ctx.lib.ifcbk_conv2d_fwd_mblocks(C.byref(gd))
-                        lst.add(_lib.OP_CONV_FWD, '+'.join(m.name for m in g.members),
-                                p=(self._aptr(g.x), _vp(self.Wsh, self.esize * g.w_off), _vp(g.raw), _vp(self.bn_part[0])),
-                                conv=gd, lane=0, reads=[ra(g.x)], writes=[('gr', id(g), 0, g.Ktot), rbp(0)])
-                        for m in g.members:
-                            mbk = m.bn_key
-                            mraw, mld = self._raw_ptr(m)
-                            mbnd = BnDesc(M, m.K, mld, m.y.buf.C, 1, self.cdtype, m.eps, 0.1)
-                            if m.cpool is not None:
-                                # commuted pool branch: pool the conv's slice of the merged tensor, then BatchNorm the pooled tensor
-                                Lm, pn = lane_of[m], m.cpool
-                                pre, ldpre = self._pre_ptr(m)
-                                ppd = PoolDesc(N, pn.x.H, pn.x.W, m.K, ldpre, 3, 3, 1, 1, 1, 1, pn.P, pn.Q, mld, self.cdtype)
-                                rpre, rr2 = ('gr', id(g), m.koff, m.koff + m.K), ('r', m.raw.id, 0, m.K)
-                                lst.add(_lib.OP_AVGPOOL_FWD, pn.name + '(' + m.name + ')', p=(pre, mraw), pool=ppd, lane=Lm,
-                                        reads=[rpre], writes=[rr2])
-                                lst.add(_lib.OP_BN_STATS, m.name, p=(mraw, _vp(self.bn_part[Lm])), bn=mbnd, lane=Lm,
-                                        reads=[rr2], writes=[rbp(Lm)])
-                                lst.add(_lib.OP_BN_FINALIZE, m.name,
-                                        p=(_vp(self.bn_part[Lm]), self._pptr(mbk + '.weight'), self._pptr(mbk + '.bias'),
-                                           _vp(self.bviews[mbk + '.running_mean']), _vp(self.bviews[mbk + '.running_var']),
-                                           self._stat(m, 0), self._stat(m, 1), self._stat(m, 2), self._stat(m, 3)),
-                                        i=(self.ctx.lib.ifcbk_bn_stats_rows(M), m.K), bn=mbnd, lane=Lm, reads=[rbp(Lm)], writes=[rst(m)])
-                                lst.add(_lib.OP_BN_APPLY, m.name,
-                                        p=(mraw, self._stat(m, 2), self._stat(m, 3), None, self._aptr(m.y)), i=(0,), bn=mbnd,
-                                        lane=Lm, reads=[rr2, rst(m)], writes=[ra(m.y)])
-                                continue
-                            # (one finalize per member, not per group: with all 29 member finalizes of the training forward REMOVED
-                            # -- timing only -- the step gains 0.15-0.22 ms; merging them into 11 launches could recover part of that)
-                            lst.add(_lib.OP_BN_FINALIZE, m.name,
-                                    p=(_vp(self.bn_part[0], 4 * m.koff), self._pptr(mbk + '.weight'), self._pptr(mbk + '.bias'),
-                                       _vp(self.bviews[mbk + '.running_mean']), _vp(self.bviews[mbk + '.running_var']),
-                                       self._stat(m, 0), self._stat(m, 1), self._stat(m, 2), self._stat(m, 3)),
-                                    i=(gmb, g.Ktot), bn=mbnd, lane=lane_of[m], reads=[rbp(0)], writes=[rst(m)])
-                            lst.add(_lib.OP_BN_APPLY, m.name,
-                                    p=(mraw, self._stat(m, 2), self._stat(m, 3), None, self._aptr(m.y)), i=(0,), bn=mbnd,
-                                    lane=lane_of[m], reads=[rraw(m), rst(m)], writes=[ra(m.y)])
-                        continue
-                    if u8:
-                        lst.add(_lib.OP_STEM_U8_FWD, n.name, p=(gu8, self._pptr(ckey), gab, raw, _vp(self.bn_part[L]), None, None),
-                                conv=dfw, lane=L, reads=[ra(n.x)], writes=[rraw(n), rbp(L)])
-                    else:
-                        lst.add(_lib.OP_CONV_FWD, n.name, p=(self._aptr(n.x), wk, raw, _vp(self.bn_part[L]) if train else None),
-                                conv=dfw, lane=L, reads=[ra(n.x)], writes=[rraw(n), rbp(L)])
-                    if train:
-                        lst.add(_lib.OP_BN_FINALIZE, n.name,
-                                p=(_vp(self.bn_part[L]), self._pptr(bkey + '.weight'), self._pptr(bkey + '.bias'),
-                                   _vp(self.bviews[bkey + '.running_mean']), _vp(self.bviews[bkey + '.running_var']),
-                                   self._stat(n, 0), self._stat(n, 1), self._stat(n, 2), self._stat(n, 3)),
-                                i=(mb,), bn=bnd, lane=L, reads=[rbp(L)], writes=[rst(n)])
-                    if train and n in fused_pool:
-                        pn, pk = fused_pool[n]
-                        ppd = PoolDesc(N, pn.x.H, pn.x.W, pn.x.C, ldraw, 3, 3, 2, 2, pn.ph, pn.pw, pn.P, pn.Q, pn.y.buf.C,
-                                       self.cdtype)
-                        lst.add(_lib.OP_BN_APPLY_MAXPOOL, n.name + '+' + pn.name,
-                                p=(raw, self._stat(n, 2), self._stat(n, 3), self._aptr(pn.y), _vp(self.argmax[pk])),
-                                i=(1,), pool=ppd, lane=L, reads=[rraw(n), rst(n)], writes=[ra(pn.y), ram(pk)])
-                        continue
-                    lst.add(_lib.OP_BN_APPLY, n.name,
-                            p=(raw, self._stat(n, 2 if train else 4), self._stat(n, 3 if train else 5), res, self._aptr(n.y)),
-                            i=(ldr,), bn=bnd, lane=L, reads=[rraw(n), rst(n)] + ([ra(n.residual)] if n.residual is not None else []),
-                            writes=[ra(n.y)])
-                evalprep.add(_lib.OP_BN_FINALIZE, n.name,
-                             p=(None, self._pptr(bkey + '.weight'), self._pptr(bkey + '.bias'),
-                                _vp(self.bviews[bkey + '.running_mean']), _vp(self.bviews[bkey + '.running_var']),
-                                None, None, self._stat(n, 4), self._stat(n, 5)), i=(0,), bn=bnd)
-                needs_dgrad = not n.x.buf.is_input
-                pack.add(_lib.OP_WEIGHT_PACK, n.name, p=(self._pptr(ckey), wk, wT if needs_dgrad else None), i=(n.wT_ld,), conv=d)
-                # ---- backward of this node
-                draw = _vp(self.draw[L]) if (g is None or n.cpool is not None) else _vp(self.draw_group, self.esize * n.koff)
-                # (flags resolved later, in reverse order) -> store a closure
-                bwd_groups.append(('conv', n, d, bnd, draw, wT, needs_dgrad))
-            elif n.kind in ('max', 'avg'):
-                pd = PoolDesc(N, n.x.H, n.x.W, n.x.C, n.x.buf.C, n.R, n.S, n.sh, n.sw, n.ph, n.pw, n.P, n.Q, n.y.buf.C,
-                              self.cdtype)
-                for lst, train in ((fwd_t, True), (fwd_e, False)):
-                    if n.aux and not train:
-                        continue
-                    if n in absorbed:
-                        continue                  # runs behind its 1x1 conv, on that conv's output (see __init__)
-                    Lx = L if train else lane_eval[n]
-                    if n.kind == 'max':
-                        if train and n in fused_pool_nodes:
-                            continue              # done by the producing conv's bn_apply_maxpool
-                        if not train and n in fused_pool_eval_nodes:
-                            continue              # done in the producing conv's epilogue
-                        lst.add(_lib.OP_MAXPOOL_FWD, n.name, p=(self._aptr(n.x), self._aptr(n.y), _vp(self.argmax[k]) if train else None), pool=pd,
-                                lane=Lx, reads=[ra(n.x)], writes=[ra(n.y), ram(k)])
-                    else:
-                        lst.add(_lib.OP_AVGPOOL_FWD, n.name, p=(self._aptr(n.x), self._aptr(n.y)), pool=pd,
-                                lane=Lx, reads=[ra(n.x)], writes=[ra(n.y)])
-                bwd_groups.append(('pool', n, pd, k))
-            elif n.kind == 'head':
-                hd = HeadDesc(N, n.HW, n.C, n.x.buf.C, n.NC, self.cdtype, 2.0)
-                wkey, bkey = n.key + '.weight', n.key + '.bias'
-                for lst, train in ((fwd_t, True), (fwd_e, False)):
-                    if n.aux and not train:
-                        continue
-                    mask = _vp(n.mask) if (train and n.dropout) else None
-                    lst.add(_lib.OP_HEAD_FWD, n.name,
-                            p=(self._aptr(n.x), mask, self._pptr(wkey) if n.fc else None, self._pptr(bkey) if n.fc else None,
-                               _vp(n.feat), _vp(n.logits)), head=hd,
-                            lane=L if train else lane_eval[n], reads=[ra(n.x)], writes=[('hd', id(n), 0, 1)])
-                bwd_groups.append(('head', n, hd))
-            elif n.kind == 'cb':
-                # conv (+bias) (+ReLU) without BatchNorm: the bias is the epilogue's shift (scale = 1), read from the fp32 master
-                d = self._conv_desc(n, N)
-                wk = _vp(self.Wsh, self.esize * n.w_off)
-                wT = _vp(self.Wsh, self.esize * n.wT_off)
-                for lst, train in ((fwd_t, True), (fwd_e, False)):
-                    Lx = L if train else lane_eval[n]
-                    if n.bias or n.relu:
-                        lst.add(_lib.OP_CONV_FWD_AFFINE, n.name,
-                                p=(self._aptr(n.x), wk, self._aptr(n.y), _vp(self.ones),
-                                   self._pptr(n.key + '.bias') if n.bias else _vp(self.zeros_k(n.K)), None),
-                                i=(0,), flags=4 if n.relu else 0, conv=d, lane=Lx, reads=[ra(n.x)], writes=[ra(n.y)])
-                    else:
-                        lst.add(_lib.OP_CONV_FWD, n.name, p=(self._aptr(n.x), wk, self._aptr(n.y), None), conv=d, lane=Lx,
-                                reads=[ra(n.x)], writes=[ra(n.y)])
-                needs_dgrad = not n.x.buf.is_input
-                pack.add(_lib.OP_WEIGHT_PACK, n.name, p=(self._pptr(n.key + '.weight'), wk, wT if needs_dgrad else None),
-                         i=(n.K if n.K != n.K_real else 0,), conv=self._pack_desc(n, d))      # wT rows keep the PADDED stride
-                bwd_groups.append(('cb', n, d, wT, needs_dgrad))
-            elif n.kind == 'drop':
-                cnt = N * n.x.H * n.x.W * n.x.C
-                for lst, train in ((fwd_t, True), (fwd_e, False)):
-                    lst.add(_lib.OP_DROPOUT, n.name, p=(self._aptr(n.x), _vp(n.mask) if train else None, self._aptr(n.y)),
-                            i=(cnt, self.cdtype), f=(1.0 / (1.0 - n.p),), lane=L if train else lane_eval[n],
-                            reads=[ra(n.x), ('dm', id(n), 0, 1)], writes=[ra(n.y)])
-                bwd_groups.append(('drop', n, cnt))
-            elif n.kind == 'flat':
-                fi = (N, n.x.H * n.x.W, n.x.C, n.x.buf.C | (self.cdtype << 32))
-                for lst, train in ((fwd_t, True), (fwd_e, False)):
-                    lst.add(_lib.OP_FLATTEN_CHW, n.name, p=(self._aptr(n.x), self._aptr(n.y)), i=fi, flags=4,
-                            lane=L if train else lane_eval[n], reads=[ra(n.x)], writes=[ra(n.y)])
-                bwd_groups.append(('flat', n, fi))
-            elif n.kind == 'bnr':
-                # BatchNorm -> ReLU in FRONT of a conv, on a channel slice of a concatenation (densenet)
-                M = N * n.x.H * n.x.W
-                bkey = n.bn_key
-                bnd = BnDesc(M, n.K, n.x.buf.C, n.K, 1 if n.relu else 0, self.cdtype, n.eps, 0.1)
-                xp = self._aptr(n.x)
-                fwd_t.add(_lib.OP_BN_STATS, n.name, p=(xp, _vp(self.bn_part[L])), bn=bnd, lane=L, reads=[ra(n.x)], writes=[rbp(L)])
-                fwd_t.add(_lib.OP_BN_FINALIZE, n.name,
-                          p=(_vp(self.bn_part[L]), self._pptr(bkey + '.weight'), self._pptr(bkey + '.bias'),
-                             _vp(self.bviews[bkey + '.running_mean']), _vp(self.bviews[bkey + '.running_var']),
-                             self._stat(n, 0), self._stat(n, 1), self._stat(n, 2), self._stat(n, 3)),
-                          i=(self.ctx.lib.ifcbk_bn_stats_rows(M), n.K), bn=bnd, lane=L, reads=[rbp(L)], writes=[rst(n)])
-                for lst, train in ((fwd_t, True), (fwd_e, False)):
-                    lst.add(_lib.OP_BN_APPLY, n.name,
-                            p=(xp, self._stat(n, 2 if train else 4), self._stat(n, 3 if train else 5), None, self._aptr(n.y)),
-                            i=(0,), bn=bnd, lane=L if train else lane_eval[n], reads=[ra(n.x), rst(n)], writes=[ra(n.y)])
-                evalprep.add(_lib.OP_BN_FINALIZE, n.name,
-                             p=(None, self._pptr(bkey + '.weight'), self._pptr(bkey + '.bias'),
-                                _vp(self.bviews[bkey + '.running_mean']), _vp(self.bviews[bkey + '.running_var']),
-                                None, None, self._stat(n, 4), self._stat(n, 5)), i=(0,), bn=bnd)
-                bwd_groups.append(('bnr', n, bnd))
-
-        # ---- grouped weight gradients (round 4): the wide-tile wgrads of one block that share a channel tile run as ONE split-K
-        # grid (ifcbk_conv2d_wgrad_group) behind the block's LAST such layer -- 1/n of the slab traffic and reduce work per layer,
-        # n times the K-steps per block.  Each member keeps its d(raw) in a buffer of its own until the group has run (the per-lane
-        # scratch is reused by the next layer's BatchNorm backward).  IFCBK_WGRAD_GROUP=0 switches it off.
-        wg_of, wg_groups = {}, []
-        if os.environ.get('IFCBK_WGRAD_GROUP', '1') != '0' and self.dtype == 'bf16':
-            buckets = {}
-            for gsp in reversed(bwd_groups):
-                if gsp[0] != 'conv':
-                    continue
-                n = gsp[1]
-                if n.group is not None or n.aux or (self.stem_u8 is n and self.in_kind[self.in_slot] == 'u8'):
-                    continue
-                dbw = ConvDesc.from_buffer_copy(gsp[2])
-                dbw.ldy = n.K
-                khv = self.ctx.lib.ifcbk_conv2d_wgrad_group_member_kh(C.byref(dbw))
-                if khv <= 0:
-                    continue
-                key = n.name.split('.')[0] if net.name == 'inception_v3' else n.name.rsplit('.', 1)[0]
-                buckets.setdefault((key, khv), []).append((n, dbw))
-            for (key, khv), mem in buckets.items():
-                for c0 in range(0, len(mem), 6):
-                    part = mem[c0:c0 + 6]
-                    if len(part) < 2:
-                        continue
-                    descs = (ConvDesc * len(part))(*[m[1] for m in part])
-                    need = self.ctx.lib.ifcbk_conv2d_wgrad_group_workspace(len(part), descs)
-                    if need == 0:
-                        continue                      # the library keeps such layers on their single launches
-                    grp_obj = dict(members=[m[0] for m in part], descs=[m[1] for m in part], ws=need, kh=khv, key=key)
-                    wg_groups.append(grp_obj)
-                    for m in part:
-                        wg_of[m[0]] = grp_obj
-            if wg_groups:
-                # (a growth here moves the arenas under the graphs of the plans built so far: _grow_workspace drops them)
-                self._grow_workspace(self.ctx, max(gq['ws'] for gq in wg_groups))
-                for gq in wg_groups:
-                    for m in gq['members']:
-                        own_draw(m)
-        self.wgrad_groups = wg_groups
-
-        # backward in reverse node order, resolving first-writer / accumulate flags
-        for g in reversed(bwd_groups):
-            if g[0] == 'head':
-                _, n, hd = g
-                wkey, bkey = n.key + '.weight', n.key + '.bias'
-                assert n.x.is_full
-                acc = acc_flag(n.x.buf)
-                assert acc == 0, 'head must be the first writer of its input gradient'
-                bwd.add(_lib.OP_HEAD_BWD, n.name,
-                        p=(_vp(n.dlogits), _vp(n.feat), _vp(n.mask) if n.dropout else None, self._pptr(wkey) if n.fc else None,
-                           self._pptr(wkey, 'G') if n.fc else None, self._pptr(bkey, 'G') if n.fc else None, self._aptr(n.x, True)),
-                        i=(n.x.buf.C,), head=hd, lane=lane_of[n], reads=[('hd', id(n), 0, 1)], writes=[rg(n.x)])
-            elif g[0] == 'cb':
-                _, n, d, wT, needs_dgrad = g
-                L = lane_of[n]
-                M = N * n.P * n.Q
-                dy, ldy = self._aptr(n.y, True), n.y.buf.C
-                if n.relu or n.bias:
-                    # dz = dy * (y > 0) in place, dbias = column sums of dz
-                    bnd = BnDesc(M, n.K, ldy, ldy, 1 if n.relu else 0, self.cdtype, 0.0, 0.0)
-                    bwd.add(_lib.OP_BIAS_RELU_BWD, n.name,
-                            p=(self._aptr(n.y), dy, dy if n.relu else None, self._pptr(n.key + '.bias', 'G') if n.bias else None),
-                            i=(ldy,), bn=bnd, lane=L, reads=[ra(n.y), rg(n.y)], writes=[rg(n.y)])
-                bwd.add(_lib.OP_CONV_WGRAD, n.name, p=(self._aptr(n.x), dy, self._pptr(n.key + '.weight', 'G')), conv=d, lane=L,
-                        reads=[ra(n.x), rg(n.y)], writes=[])
-                if needs_dgrad:
-                    assert n.x.is_full
-                    acc = acc_flag(n.x.buf)
-                    bwd.add(_lib.OP_CONV_DGRAD, n.name, p=(dy, wT, self._aptr(n.x, True)), flags=acc, conv=d, lane=L,
-                            reads=[rg(n.y)], writes=[rg(n.x)])
-            elif g[0] == 'drop':
-                _, n, cnt = g
-                acc = acc_flag(n.x.buf)
-                bwd.add(_lib.OP_DROPOUT, n.name, p=(self._aptr(n.y, True), _vp(n.mask), self._aptr(n.x, True)), i=(cnt, self.cdtype),
-                        f=(1.0 / (1.0 - n.p),), flags=acc, lane=lane_of[n], reads=[rg(n.y), ('dm', id(n), 0, 1)], writes=[rg(n.x)])
-            elif g[0] == 'flat':
-                _, n, fi = g
-                assert n.x.is_full
-                acc = acc_flag(n.x.buf)
-                bwd.add(_lib.OP_FLATTEN_CHW, n.name, p=(self._aptr(n.x, True), self._aptr(n.y, True)), i=fi, flags=acc,
-                        lane=lane_of[n], reads=[rg(n.y)], writes=[rg(n.x)])
-            elif g[0] == 'bnr':
-                _, n, bnd = g
-                bkey = n.bn_key
-                # the slice's gradient: the FIRST backward op that touches the concatenation must cover all of it (densenet: the
-                # transition / norm5 that reads the whole block output); later (= earlier-in-forward) layers accumulate
-                first = n.x.buf.id not in written
-                if first:
-                    assert n.x.is_full, 'the first gradient written into a concatenation must cover all of it: ' + n.name
-                acc = acc_flag(n.x.buf)
-                bwd.add(_lib.OP_BN_BWD, n.name,
-                        p=(self._aptr(n.x), self._aptr(n.y), self._aptr(n.y, True), self._pptr(bkey + '.weight'),
-                           self._stat(n, 0), self._stat(n, 1), self._aptr(n.x, True), None, self._pptr(bkey + '.weight', 'G'),
-                           self._pptr(bkey + '.bias', 'G'), self._stat(n, 2), self._stat(n, 3)),
-                        i=(n.K, n.x.buf.C, 0), flags=8 if acc else 0, bn=bnd, lane=lane_of[n],
-                        reads=[ra(n.x), ra(n.y), rg(n.y), rst(n)], writes=[rg(n.x)])
-            elif g[0] == 'pool':
-                _, n, pd, k = g
-                assert n.x.is_full
-                if n in fused_pool_nodes:
-                    continue                      # gathered inside the producer's bn_bwd_maxpool
-                if n in absorbed:
-                    continue                      # its gradient reaches x through the sibling GEMM's input gradient
-                acc = acc_flag(n.x.buf)
-                if n.kind == 'max':
-                    bwd.add(_lib.OP_MAXPOOL_BWD, n.name, p=(self._aptr(n.y, True), _vp(self.argmax[k]), self._aptr(n.x, True)), flags=acc, pool=pd,
-                            lane=lane_of[n], reads=[rg(n.y), ram(k)], writes=[rg(n.x)])
-                else:
-                    bwd.add(_lib.OP_AVGPOOL_BWD, n.name, p=(self._aptr(n.y, True), self._aptr(n.x, True)), flags=acc, pool=pd,
-                            lane=lane_of[n], reads=[rg(n.y)], writes=[rg(n.x)])
-            else:
-                _, n, d, bnd, draw, wT, needs_dgrad = g
-                wgq = wg_of.get(n)
-                own = wgq is not None or (self.wgrad_lane and (n.group is None or n.cpool is not None))
-                if own:
-                    draw = _vp(own_draw(n))               # kept until the (grouped / lane's) weight gradient has read it
-                elif self.wgrad_lane:
-                    draw = _vp(group_draw(n.group), self.esize * n.koff)
-                LW = None                                 # lane of this node's weight gradient (None: the node's own lane)
-                if self.wgrad_lane:
-                    LW = WLs[wl_next[0] % len(WLs)]       # (round-robin over the weight-gradient lanes, per NODE)
-                    wl_next[0] += 1
-                ckey, bkey = n.conv_key + '.weight', n.bn_key
-                dres, lddres, dres_acc = None, 0, 0
-                if n.residual is not None:
-                    assert n.residual.is_full
-                    dres_acc = acc_flag(n.residual.buf)
-                    dres, lddres = self._aptr(n.residual, True), n.residual.buf.C
-                grp = n.group
-                L = lane_of[n]
-                cp = n.cpool is not None
-                rdraw = [rdg(n)] if (grp is not None and not cp) else [('draw', L, 0, 1)]     # d(raw): merged-group slice or the lane's scratch
-                if own:
-                    rdraw = [('drawn', id(n), 0, 1)]
-                rawp, _ld = self._raw_ptr(n)
-                if n in fused_pool:
-                    pn, pk = fused_pool[n]
-                    ppd = PoolDesc(N, pn.x.H, pn.x.W, pn.x.C, _ld, 3, 3, 2, 2, pn.ph, pn.pw, pn.P, pn.Q, pn.y.buf.C, self.cdtype)
-                    bwd.add(_lib.OP_BN_BWD_MAXPOOL, n.name + '+' + pn.name,
-                            p=(rawp, self._aptr(pn.y, True), _vp(self.argmax[pk]), self._pptr(bkey + '.weight'),
-                               self._stat(n, 0), self._stat(n, 1), self._stat(n, 2), self._stat(n, 3), draw,
-                               self._pptr(bkey + '.weight', 'G'), self._pptr(bkey + '.bias', 'G')),
-                            i=(1, n.K), pool=ppd, lane=L, reads=[rraw(n), rg(pn.y), ram(pk), rst(n)], writes=rdraw)
-                elif n in bnstat_done:
-                    ppart, nrow, pres = bnstat_done[n]
-                    bwd.add(_lib.OP_BN_BWD_PARTIALS, n.name,
-                            p=(rawp, self._aptr(n.y, True), self._pptr(bkey + '.weight'), self._stat(n, 0), self._stat(n, 1),
-                               self._stat(n, 2), self._stat(n, 3), ppart, draw, self._pptr(bkey + '.weight', 'G'),
-                               self._pptr(bkey + '.bias', 'G')),
-                            i=(n.y.buf.C, nrow, n.K if (grp is None or cp) else grp.Ktot, 0), bn=bnd, lane=L,
-                            reads=[rraw(n), rg(n.y), rst(n), pres], writes=rdraw)
-                else:
-                    bwd.add(_lib.OP_BN_BWD, n.name,
-                            p=(rawp, self._aptr(n.y), self._aptr(n.y, True), self._pptr(bkey + '.weight'),
-                               self._stat(n, 0), self._stat(n, 1), draw, dres, self._pptr(bkey + '.weight', 'G'),
-                               self._pptr(bkey + '.bias', 'G'), self._stat(n, 2), self._stat(n, 3)),
-                            i=(n.y.buf.C, n.K if (grp is None or cp) else grp.Ktot, lddres), flags=dres_acc, bn=bnd, lane=L,
-                            reads=[rraw(n), ra(n.y), rg(n.y), rst(n)],
-                            writes=rdraw + ([rg(n.residual)] if n.residual is not None else []))
-                if cp:
-                    # d(pooled conv output) -> d(conv output): the average pool is its own transpose; into the branch's slice of
-                    # the merged d(raw) scratch, from where the sibling GEMM's weight / input gradients pick it up
-                    pn = n.cpool
-                    ppd = PoolDesc(N, pn.x.H, pn.x.W, n.K, grp.Ktot, 3, 3, 1, 1, 1, 1, pn.P, pn.Q, n.K, self.cdtype)
-                    bwd.add(_lib.OP_AVGPOOL_BWD, pn.name + '(' + n.name + ')',
-                            p=(draw, _vp(group_draw(grp), self.esize * n.koff)), flags=0, pool=ppd, lane=L,
-                            reads=rdraw, writes=[rdg(n)])
-                if grp is not None:
-                    # fused siblings: every member's d(raw) lands in its slice of the merged scratch; the member that
-                    # comes FIRST in forward order is the last one here and launches the single wgrad + dgrad
-                    if grp.members[0] is n:
-                        gd = self._group_desc(grp, N)
-                        gdraw = group_draw(grp)
-                        gp = [_vp(gdraw)] + [self._pptr(m.conv_key + '.weight', 'G') for m in grp.members]
-                        gres = ('dg', id(grp), 0, grp.Ktot)
-                        bwd.add(_lib.OP_CONV_WGRAD_SEG, '+'.join(m.name for m in grp.members),
-                                p=[self._aptr(grp.x), gp[0]] + gp[1:], i=[m.K for m in grp.members], conv=gd,
-                                lane=0 if LW is None else LW, reads=[ra(grp.x), gres], writes=[])
-                        acc = acc_flag(grp.x.buf)
-                        bwd.add(_lib.OP_CONV_DGRAD, '+'.join(m.name for m in grp.members),
-                                p=(_vp(gdraw), _vp(self.Wsh, self.esize * grp.wT_off), self._aptr(grp.x, True)),
-                                flags=acc, conv=gd, lane=0, reads=[gres], writes=[rg(grp.x)])
-                    continue
-                dbw = ConvDesc.from_buffer_copy(d)
-                dbw.ldy = n.K                       # dy of the conv = the dense d(raw) scratch
-                if wgq is not None:
-                    wgq.setdefault('seen', []).append(n)
-                    if len(wgq['seen']) == len(wgq['members']):
-                        # the block's last member in backward order: every member's d(raw) exists now
-                        mem = wgq['members']
-                        items = (_lib.WgradItem * len(mem))()
-                        for kq, (m, dq) in enumerate(zip(mem, wgq['descs'])):
-                            items[kq].d = dq
-                            items[kq].x = self._aptr(m.x).value
-                            items[kq].dy = self.draw_own[m].data_ptr()
-                            items[kq].dw = self._pptr(m.conv_key + '.weight', 'G').value
-                        keep.append(items)
-                        bwd.add(_lib.OP_CONV_WGRAD_GROUP, '+'.join(m.name for m in mem),
-                                p=[C.addressof(items)] + [items[kq].dw for kq in range(len(mem))], i=(len(mem),), lane=L if LW is None else LW,
-                                reads=[ra(m.x) for m in mem] + [('drawn', id(m), 0, 1) for m in mem], writes=[])
-                elif self.stem_u8 is n and self.in_kind[self.in_slot] == 'u8':
-                    bwd.add(_lib.OP_STEM_U8_WGRAD, n.name,
-                            p=(_vp(self.in_u8[self.in_slot]), draw, _vp(self.in_ab[self.in_slot]), self._pptr(ckey, 'G')), conv=dbw,
-                            lane=L if LW is None else LW, reads=[ra(n.x)] + rdraw, writes=[])
-                else:
-                    bwd.add(_lib.OP_CONV_WGRAD, n.name, p=(self._aptr(n.x), draw, self._pptr(ckey, 'G')), conv=dbw,
-                            lane=L if LW is None else LW,
-                            reads=[ra(n.x)] + rdraw, writes=[])
-                if needs_dgrad:
-                    assert n.x.is_full
-                    acc = acc_flag(n.x.buf)
-                    if n in bnstat_of and acc == 0:
-                        pn = bnstat_of[n]
-                        prow, pld = self._raw_ptr(pn)
-                        nrow = self.ctx.lib.ifcbk_conv2d_dgrad_bnstat_mblocks(C.byref(dbw))
-                        bwd.add(_lib.OP_CONV_DGRAD_BNSTAT, n.name,
-                                p=(draw, wT, self._aptr(n.x, True), prow, self._stat(pn, 0), self._stat(pn, 1),
-                                   self._stat(pn, 2), self._stat(pn, 3), _vp(self.bn_part[L])), i=(pld,), conv=dbw,
-                                lane=L, reads=rdraw + [rraw(pn), rst(pn)], writes=[rg(n.x), rbp(L)])
-                        bnstat_done[pn] = (_vp(self.bn_part[L]), nrow, rbp(L))
-                    else:
-                        bwd.add(_lib.OP_CONV_DGRAD, n.name, p=(draw, wT, self._aptr(n.x, True)), flags=acc, conv=dbw,
-                                lane=L, reads=rdraw, writes=[rg(n.x)])
-
-        class PlanObj:
-            pass
-        pl = PlanObj()
-        pl.N = N
-        pl.fwd_train, pl.fwd_eval, pl.bwd = Program(fwd_t), Program(fwd_e), Program(bwd)
-        pack_ops = pack                                # one OP_WEIGHT_PACK per conv (the bucketed update cuts this list)
-        pack = self._pack_multi(pack)
-        pl.pack, pl.evalprep = Program(pack), Program(evalprep)
-        # loss ops: CE(main) + 0.4*CE(aux)   (neuston_models.py:70-78)
-        lossl = OpList()
-        main = [h for h in self.heads if not h.aux][0]
-        auxh = [h for h in self.heads if h.aux]
-        # with class weights (TRAIN --class-norm): the same three ops as OP_SOFTMAX_XENT_W, the weight tensor as a fifth operand.
-        # Loss ops carry no lane annotation: they are full barriers on lane 0, so the read-only weight tensor needs no resource entry
-        xent, cw = (_lib.OP_SOFTMAX_XENT, ()) if self.class_weight is None else (_lib.OP_SOFTMAX_XENT_W, (_vp(self.class_weight),))
-        # label smoothing (TRAIN --label-smoothing) is the second scalar of the same ops, either kind: f[1] != 0 sends the op to the
-        # smoothed kernel (ifcbk_softmax_xent_ls); without it f[1] stays the zero of a fresh op and the tables are what they were
-        ls = (self.label_smoothing,) if self.label_smoothing > 0 else ()
-        # the focusing exponent (TRAIN --focal-gamma) is the third scalar: f[2] != 0 sends the op to ifcbk_softmax_xent_focal; the
-        # engine refuses the two together, so f[1] is then the zero it writes here
-        if self.focal_gamma > 0:
-            ls = (0.0, self.focal_gamma)
-        # the factors of a mixed batch (TRAIN --mixup / --cutmix) are a sixth operand of the TRAIN loss ops: p[5] != NULL sends the op to
-        # ifcbk_softmax_xent_mix; the validation loss below stays the one-target loss.  Without mix the tuples are what they were
-        mx = ((None,) * (1 - len(cw)) + (_vp(self.mix_lam[self.in_slot]),)) if self.mix else ()
-        # a teacher's logits (TRAIN --distill) are a seventh operand of the TRAIN loss ops, with alpha and the temperature as f[3], f[4]:
-        # p[6] != NULL sends the op to ifcbk_softmax_xent_distill; both heads of inception_v3 distil from the teacher's one set of logits,
-        # and the validation loss below stays the hard loss.  Without distill the tuples are what they were
-        ds, dsf = (), ()
-        if self.distill is not None:
-            ds = (None,) * (2 - len(cw)) + (_vp(self.teacher_logits),)
-            dsf = (0.0,) * (2 - len(ls)) + self.distill
-        lossl.add(xent, 'loss', p=(_vp(main.logits), _vp(self.target), _vp(self.loss), _vp(main.dlogits)) + cw + mx + ds,
-                  i=(N, net.NC), f=(1.0,) + ls + dsf)
-        for h in auxh:
-            lossl.add(xent, 'loss_aux', p=(_vp(h.logits), _vp(self.target), _vp(self.loss), _vp(h.dlogits)) + cw + mx + ds,
-                      i=(N, net.NC), f=(0.4,) + ls + dsf, flags=1)
-        pl.loss = Program(lossl)
-        evl = OpList()
-        evl.add(xent, 'val_loss', p=(_vp(main.logits), _vp(self.target), _vp(self.loss), None) + cw, i=(N, net.NC), f=(1.0,) + ls)
-        pl.eval_loss = Program(evl)
-        sm = OpList()
-        sm.add(_lib.OP_SOFTMAX, 'softmax', p=(_vp(main.logits), _vp(self.probs)), i=(N, net.NC))
-        pl.softmax = Program(sm)
-        opt = OpList()
-        # the weight average (TRAIN --ema) is one more operand of the optimizer op, behind those of the plain step: E at the offset of P
-        # (every bucket's op below carries its slice); its weight is stamped per step (_set_update).  Without it the tuples are what they were
-        ema = (_vp(self.E),) if self.ema_decay is not None else ()
-        if self.optimizer == 'sgd':
-            # additive option (north_star "SGD/Adam step"; upstream only has Adam): torch.optim.SGD's update, momentum buffer = M
-            opt.add(_lib.OP_SGD, 'sgd', p=(_vp(self.P), _vp(self.G), _vp(self.M) if self.momentum else None) + ema,
-                    i=(self.nparam_padded, 1), f=(self.lr, self.momentum, self.weight_decay, 1.0))
-        else:
-            opt.add(_lib.OP_ADAM, 'adam', p=(_vp(self.P), _vp(self.G), _vp(self.M), _vp(self.V)) + ema,
-                    i=(self.nparam_padded, 1), f=(self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, 1.0))
-        pl.adam = Program(opt)
-        # the step's bookkeeping in the step's own op table: num_batches_tracked += 1 of every BatchNorm, loss_sum += loss
-        cnt = OpList()
-        cnt.add(_lib.OP_STEP_COUNTERS, 'step_counters', p=(_vp(self.nbt), _vp(self.loss_sum), _vp(self.loss)), i=(self.nbt.numel(),))
-        # fused train step = fwd + loss + bwd + adam + pack (+ counters); round 5: the optimizer and the repack run PER BUCKET of the
-        # flat gradient buffer, on the weight-gradient lane, as soon as backward has finished the bucket (_bucketed_update)
-        allops = OpList()
-        for prog_ops in (fwd_t, lossl) + self._bucketed_update(bwd, opt, pack_ops) + (cnt,):
-            allops.extend(prog_ops)
-        pl.step = Program(allops)
-        pl.step_adam_idxs = pl.step.find(_lib.OP_SGD if self.optimizer == 'sgd' else _lib.OP_ADAM)
-        pl.step_adam_idx = pl.step_adam_idxs[-1]
-        # data-parallel variant: fwd+loss | backward segments (all-reduce launched after each) | adam+pack
-        fl = OpList()
-        fl.extend(fwd_t)
-        fl.extend(lossl)
-        pl.fwd_loss = Program(fl)
-        fb = OpList()
-        for prog_ops in (fwd_t, lossl, bwd):
-            fb.extend(prog_ops)
-        pl.fwd_bwd = Program(fb)          # the part of a train step whose launch arguments never change: hipGraph-capturable
-        pl.graphs = {}
-        ap = OpList()
-        ap.extend(opt)
-        ap.extend(pack)
-        ap.extend(cnt)
-        pl.adam_pack = Program(ap)
-        pl.bwd_list = bwd
-        pl.ddp_segs = None
-        pl.keep = keep
-        return pl
-
-    def _bucketed_update(self, bwd, opt, pack_ops):
-        """-> (backward ops with the optimizer + repack of every finished gradient bucket inserted, the last bucket's optimizer, its
-        repack).  Backward finishes the flat gradient buffer from its tail (dp.segment_plan: the cuts of the data-parallel exchange);
-        a bucket's optimizer op and the repack of its conv weights go onto the weight-gradient lane right behind the ops that
-        complete it -- and behind the last input-gradient op that reads a bf16 shadow of the bucket (the shadow is rewritten by the
-        repack) -- so that only the last bucket (the stem: 4 % of the parameters) is updated behind the end of backward.  Same
-        arithmetic per element as one launch over the whole buffer (Adam / SGD are element-wise; the step count is a launch
-        argument of every bucket's op).  IFCBK_OPT_BUCKETS: target number of buckets (6), <= 1 = one launch at the end."""
-        nb = int(os.environ.get('IFCBK_OPT_BUCKETS', '6'))
-        whole = (bwd, opt, self._pack_multi(pack_ops))
-        if nb <= 1:
-            return whole
-        from .dp import segment_plan
-        offs = [self._op_param_offsets(o) for o in bwd.ops]
-        try:
-            segs = segment_plan(offs, self.palloc, self.nparam_padded, nb)
-        except RuntimeError:
-            return whole
-        if len(segs) < 2:
-            return whole
-        # which parameters' shadows does an input-gradient op read?  (a sibling group's op: every member's)
-        pbase, sbase = self.P.data_ptr(), self.Wsh.data_ptr()
-        regions = [(g.wT_off, g.wT_off + g.Ktot * g.x.C) for g in self.groups]
-
-        def skey(elem_off):
-            for (r0, r1) in regions:
-                if r0 <= elem_off < r1:
-                    return r0
-            return elem_off
-        owners = {}
-        for o in pack_ops.ops:
-            if o.p[2]:
-                owners.setdefault(skey((o.p[2] - sbase) // self.esize), []).append((o.p[0] - pbase) // 4)
-        dkinds = (_lib.OP_CONV_DGRAD, _lib.OP_CONV_DGRAD_BNSTAT)
-        last_reader = {}                       # parameter offset -> index of the last backward op that reads its shadow
-        shreads = {}                           # backward op index -> [('SH', off, off + size)]
-        for k, o in enumerate(bwd.ops):
-            if o.kind in dkinds:
-                own = owners.get(skey((o.p[1] - sbase) // self.esize))
-                if own is None:
-                    return whole               # an input gradient whose filter this plan cannot attribute: keep the single update
-                shreads[k] = [('SH', off, off + self.palloc[off]) for off in own]
-                for off in own:
-                    last_reader[off] = k
-        LW = self.NL - 1 if self.wgrad_lane else 0
-        # pointer operands of the optimizer op: P, G, M (, V) and, with a weight average, its slice of E behind them
-        nptr = (4 if self.optimizer != 'sgd' else 3) + (1 if self.ema_decay is not None else 0)
-        inserts = {}                           # op index -> OpList to emit BEFORE that op (i.e. behind op index - 1)
-        prev_ins = 0
-        for (b0, b1, lo, hi) in segs[:-1]:
-            ins = max([b1, prev_ins] + [1 + k for off, k in last_reader.items() if lo <= off < hi])
-            prev_ins = ins
-            ol = inserts.setdefault(ins, OpList())
-            o0 = opt.ops[0]
-            ptrs = [(o0.p[j] + 4 * lo) if o0.p[j] else None for j in range(nptr)]
-            ol.add(o0.kind, opt.tags[0] + '[%d:%d]' % (lo, hi), p=ptrs, i=(hi - lo, int(o0.i[1])), f=tuple(o0.f[j] for j in range(8)),
-                   lane=LW, reads=[('G', lo, hi)], writes=[('P', lo, hi)] + ([('E', lo, hi)] if self.ema_decay is not None else []))
-            sub = OpList()
-            for o, tg, mt in zip(pack_ops.ops, pack_ops.tags, pack_ops.meta):
-                if lo <= (o.p[0] - pbase) // 4 < hi:
-                    sub.ops.append(o); sub.tags.append(tg); sub.meta.append(mt)
-            if sub.ops:
-                pm = self._pack_multi(sub, key=(lo, hi))
-                pm.meta[0] = (LW, [('P', lo, hi)], [('SH', lo, hi)])
-                ol.extend(pm)
-        out = OpList()
-        for k, (o, tg, mt) in enumerate(zip(bwd.ops, bwd.tags, bwd.meta)):
-            if k in inserts:
-                out.extend(inserts[k])
-            lane, reads, writes = mt
-            if not (reads is None and writes is None):
-                extra_w = [('G', off, off + self.palloc[off]) for off in offs[k]]
-                mt = (lane, list(reads or ()) + shreads.get(k, []), list(writes or ()) + extra_w)
-            out.ops.append(o); out.tags.append(tg); out.meta.append(mt)
-        for k in sorted(inserts):
-            if k >= len(bwd.ops):
-                out.extend(inserts[k])
-        # the last bucket: behind the end of backward, as full barriers (as the single update was)
-        lo, hi = segs[-1][2], segs[-1][3]
-        last_opt, last_pack = OpList(), OpList()
-        o0 = opt.ops[0]
-        ptrs = [(o0.p[j] + 4 * lo) if o0.p[j] else None for j in range(nptr)]
-        last_opt.add(o0.kind, opt.tags[0] + '[%d:%d]' % (lo, hi), p=ptrs, i=(hi - lo, int(o0.i[1])), f=tuple(o0.f[j] for j in range(8)))
-        sub = OpList()
-        for o, tg, mt in zip(pack_ops.ops, pack_ops.tags, pack_ops.meta):
-            if lo <= (o.p[0] - pbase) // 4 < hi:
-                sub.ops.append(o); sub.tags.append(tg); sub.meta.append(mt)
-        if sub.ops:
-            last_pack = self._pack_multi(sub, key=(lo, hi))
-        return (out, last_opt, last_pack)
 
     def _pack_multi(self, pack, key=None):
         """fold the per-conv weight_pack ops into ONE multi-tensor launch (device-side item table, built once per ``key``:

@@ -42,7 +42,7 @@ DTYPES = ('bf16', 'fp32')                       # bf16: every scenario; fp32: th
 
 # ---------------------------------------------------------------------------------------------- plan identity (CPU)
 def carves(eng):
-    """[(first byte, bytes, name)] of the d(raw) tensors carved out of the engine's pooled allocation (engine._build: _carve)"""
+    """[(first byte, bytes, name)] of the d(raw) tensors carved out of the engine's pooled allocation (Engine._carve)"""
     pool = getattr(eng, '_draw_pool', None)
     if pool is None:
         return []
@@ -184,7 +184,7 @@ def train(eng, N):
 
 def evaluate(eng, N):
     """forward_eval + eval loss + softmax -> probs[:N], loss and the logits[:N] of every head the eval forward runs (the auxiliary
-    classifier is not part of it: engine._build, `if n.aux and not train`)"""
+    classifier is not part of it: plan.PlanBuilder._fwd_conv, `if not n.aux`)"""
     pl = eng.forward_eval(N)
     eng.run(pl.eval_loss)
     eng.run(pl.softmax)

@@ -44,7 +44,22 @@ CONFIGS = {
     'inception_v3-bf16-b64-wgrad_group0': ('inception_v3', 'bf16', 64, {}, {'IFCBK_WGRAD_GROUP': '0'}),      # (no groups at b2)
     'inception_v3-bf16-b2-opt_buckets1': ('inception_v3', 'bf16', 2, {}, {'IFCBK_OPT_BUCKETS': '1'}),
     'inception_v3-bf16-b2-fuse_pool0': ('inception_v3', 'bf16', 2, {}, {'IFCBK_FUSE_POOL': '0'}),
+    'inception_v3-bf16-b2-u8': ('inception_v3', 'bf16', 2, {}, {}),                                          # (IN_KIND below)
+    'inception_v3-bf16-b64': ('inception_v3', 'bf16', 64, {}, {}),             # grouped weight gradients: the workspace grows
+    'resnet18-fp32-b2': ('resnet18', 'fp32', 2, {}, {}),
+    'inception_v3-bf16-b2-sgd': ('inception_v3', 'bf16', 2, {'optimizer': 'sgd', 'momentum': 0.9}, {}),
+    'inception_v3-bf16-b2-ema': ('inception_v3', 'bf16', 2, {'ema_decay': 0.999}, {}),
+    'inception_v3-bf16-b2-class_weights-ls': ('inception_v3', 'bf16', 2, {'class_weights': [1.0, 0.5, 2.0, 1.5, 0.25, 3.0, 1.0],
+                                                                          'label_smoothing': 0.1}, {}),
+    'inception_v3-bf16-b2-focal': ('inception_v3', 'bf16', 2, {'focal_gamma': 2.0}, {}),
+    'inception_v3-bf16-b2-mix': ('inception_v3', 'bf16', 2, {'mix': True}, {}),
+    'inception_v3-bf16-b2-distill': ('inception_v3', 'bf16', 2, {'distill': (0.5, 2.0)}, {}),
+    'inception_v3-bf16-b2-fuse_pool_eval0': ('inception_v3', 'bf16', 2, {}, {'IFCBK_FUSE_POOL_EVAL': '0'}),
+    'inception_v3-bf16-b2-fuse_siblings0': ('inception_v3', 'bf16', 2, {}, {'IFCBK_FUSE_SIBLINGS': '0'}),
 }
+
+# configurations planned on the resized u8 plane of the input slot (eng.in_kind) instead of the dense tensor
+IN_KIND = {'inception_v3-bf16-b2-u8': 'u8'}
 
 
 class Owners:
@@ -143,8 +158,9 @@ def plan_text(eng, pl):
     return '\n'.join(lines) + '\n'
 
 
-def build_plan(cfg):
-    """-> (engine, plan) of one configuration, with the environment it names (and nothing else of the switches) in force"""
+def build_plan(cfg, plan_only=True):
+    """-> (engine, plan) of one configuration, with the environment it names (and nothing else of the switches) in force;
+    plan_only=False: on an engine with a device (tests/test_gpu_plan_fingerprint.py)"""
     from unittest import mock
     import torch
     from ifcb_classifier_amd import graph
@@ -156,12 +172,15 @@ def build_plan(cfg):
     # from being touched (committed)
     with mock.patch.dict(os.environ, dict(keep, **env), clear=True), mock.patch.object(torch, 'zeros', torch.empty), \
             mock.patch.object(torch, 'zeros_like', torch.empty_like):
-        eng = Engine(graph.build(model, 7), max_batch=B, dtype=dtype, plan_only=True, **kw)
+        eng = Engine(graph.build(model, 7), max_batch=B, dtype=dtype, plan_only=plan_only, **kw)
+        if cfg in IN_KIND:
+            assert eng.stem_u8 is not None
+            eng.in_kind[eng.in_slot] = IN_KIND[cfg]
         return eng, eng.plan(B)
 
 
-def fingerprint(cfg):
-    eng, pl = build_plan(cfg)
+def fingerprint(cfg, plan_only=True):
+    eng, pl = build_plan(cfg, plan_only)
     return hashlib.sha256(plan_text(eng, pl).encode()).hexdigest()
 
 

@@ -2,7 +2,7 @@
 
 tests/test_gpu_engine_life.py holds a long-lived engine of capacity B that runs a partial batch N to the raw bits of a fresh engine of
 capacity N.  That bound is only right if both run the same program: the same op kinds, flags with lane and wait bits, descriptors,
-scalars, kernel names and symbolic pointers.  In Engine._build, max_batch and train_batch enter buffer sizes only, and the library
+scalars, kernel names and symbolic pointers.  In plan.PlanBuilder, max_batch and train_batch enter buffer sizes only, and the library
 compares the reserved workspace with what a launch needs, never picks a kernel from it; here that is checked, not assumed."""
 import os
 from unittest import mock
@@ -27,7 +27,7 @@ def test_plan_text_is_the_same_at_every_capacity(family, B, N, dtype):
     """make_plan_fingerprints.plan_text of plan(N) on a max_batch=B engine equals that on a max_batch=N engine.
 
     One field is normalised, and only that one: a d(raw) tensor carved from the engine's pooled allocation appears as
-    '_draw_pool+<byte offset>', and the offset is the sum of the earlier carves' sizes, which hold train_batch (engine._build: _carve).
+    '_draw_pool+<byte offset>', and the offset is the sum of the earlier carves' sizes, which hold train_batch (Engine._carve).
     engine_life.capacity_free rewrites it as '<carved tensor>+<offset inside the carve>'.  The raw texts are required to differ in
     nothing but lines that name the pool, and squeezenet1_1 (no BatchNorm, no pool) must be equal without any rewriting."""
     name = el.FAMILIES[family][0]

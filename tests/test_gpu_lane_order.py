@@ -199,9 +199,9 @@ def test_a_dropped_wait_is_caught(rig):
 
 @ALL
 def test_the_plans_that_ran_pass_the_footprint_audit(rig):
-    """tests/test_program_footprints_cpu.py audits Engine(plan_only=True), which differs from an engine with a device: it skips the
-    eval-mode conv + max-pool fusion (OP_CONV_FWD_AFFINE_MAXPOOL) and the workspace growth of the grouped weight gradients.  The
-    same audit over the programs that the tests above launched."""
+    """tests/test_program_footprints_cpu.py audits Engine(plan_only=True), which plans the same ops as an engine with a device (the
+    eval-mode conv + max-pool fusion, OP_CONV_FWD_AFFINE_MAXPOOL, included) but skips the workspace growth of the grouped weight
+    gradients.  The same audit over the programs that the tests above launched."""
     import program_footprints as pf
     pl = rig.pl
     for prog in ('step', 'fwd_eval', 'fwd_train', 'bwd', 'pack', 'evalprep'):

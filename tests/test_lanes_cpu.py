@@ -110,7 +110,7 @@ def test_program_lane_default_follows_the_job_size_not_the_construction_order(mo
 
 def test_bucketed_optimizer_waits_for_its_gradients_and_the_repack_for_the_readers_of_the_shadows():
     """round 5: the fused train step runs the optimizer and the bf16 repack PER BUCKET of the flat gradient buffer, on the
-    weight-gradient lane, while backward is still running (engine._bucketed_update).  On the frozen step program of inception_v3
+    weight-gradient lane, while backward is still running (plan.PlanBuilder._bucketed_update).  On the frozen step program of inception_v3
     (lanes and wait masks as ctx.hip::run_lanes will see them): the buckets tile the parameter buffer; every op that writes a
     gradient happens-before the optimizer launch of its bucket; a bucket's repack happens-after its optimizer launch AND after
     every input-gradient op that still reads the bf16 shadows it rewrites.  ref neuston_models.py:63-64,81-86: optimizer.step()

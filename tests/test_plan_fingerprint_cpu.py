@@ -3,8 +3,8 @@ configuration of tests/golden/make_plan_fingerprints.py is rebuilt and its finge
 tag, i[], f[], descriptor bytes, resolved kernel name and symbolic pointers of every op of all 13 programs -- compared with
 tests/golden/plan_fingerprints.json.  A refactor of the plan builder or of the library's planning helpers must leave them equal.
 
-One path is not covered: the eval conv + folded BatchNorm + ReLU + max-pool fusion (OP_CONV_FWD_AFFINE_MAXPOOL) is only planned
-when the engine is not plan_only (engine.py, `fused_pool_eval`); tests/test_gpu_conv_pool.py covers it on the GPU."""
+The eval conv + folded BatchNorm + ReLU + max-pool fusion (OP_CONV_FWD_AFFINE_MAXPOOL) is planned here as on a device (its one
+library call is a host function); tests/test_gpu_plan_fingerprint.py holds a device engine's plans to the same golden."""
 import json
 import os
 import sys
