@@ -21,6 +21,7 @@ if os.environ.get('IFCBK_LIB'):
 BF16, F32 = 0, 1
 MIX_U8 = 2                                                        # ifcbk_batch_mix: the u8 plane (the dense kinds are BF16 / F32)
 SYM_HFLIP, SYM_VFLIP, SYM_TRANSPOSE = 1, 2, 4                     # ifcbk_batch_sym: one op per call
+ROI_GATHER_MAX_N, ROI_GATHER_CHUNK = 4096, 16384                  # ifcbk_roi_gather: the scan's limit, destination bytes per copy block
 OK, EINVAL, EHIP, ENOMEM, EUNSUPPORTED = 0, -1, -2, -3, -4        # include/ifcbk.h
 
 (OP_CONV_FWD, OP_CONV_DGRAD, OP_CONV_WGRAD, OP_WEIGHT_PACK, OP_BN_FINALIZE, OP_BN_APPLY, OP_BN_BWD,
@@ -162,6 +163,7 @@ _PROTOS = {
     'ifcbk_roi_preprocess_fit_workspace': (_sz, [C.POINTER(RoiDesc), _i, _i]),
     'ifcbk_roi_jitter': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'ifcbk_roi_jitter_workspace': (_sz, [_i]),
+    'ifcbk_roi_gather': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, C.c_int64, _vp, _vp, _vp, _vp]),
     'ifcbk_batch_mix': (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, _vp]),
     'ifcbk_batch_sym': (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     'ifcbk_u8_channel_moments': (_i, [_vp, _vp, _i, C.c_int64, _i, _vp, _vp]),

@@ -640,6 +640,12 @@ def rois_to_device(batch, device, transform=None):
     kw = dict(pixels=batch['pixels'].to(device, non_blocking=True), offs=batch['offs'].to(device, non_blocking=True),
               hs=batch['hs'].to(device, non_blocking=True), ws=batch['ws'].to(device, non_blocking=True),
               max_h=batch['max_h'], max_w=batch['max_w'], in_channels=batch['in_channels'])
+    return attach_draws(kw, batch, device, transform)
+
+
+def attach_draws(kw, batch, device, transform=None):
+    """the second half of ``rois_to_device``: the batch's flip codes and jitter factors (``batch``: a collated batch, or ``draw_items``'
+    result) and the transform's Normalize / pad settings, added to the ``load_rois`` arguments ``kw`` of ROIs already on the device"""
     if batch.get('turn') or (transform is not None and getattr(transform, 'rot90', False)):
         # the codes may hold a transpose bit: always handed over, so the kernels a run launches do not depend on the draw
         kw['flips'] = batch['flips'].to(device, non_blocking=True)
@@ -653,3 +659,131 @@ def rois_to_device(batch, device, transform=None):
     if 'brightness' in batch or 'contrast' in batch:
         kw['jitter'] = tuple(batch[k].to(device, non_blocking=True) if k in batch else None for k in ('brightness', 'contrast'))
     return kw
+
+
+# ------------------------------------------------------------------------------------------ TRAIN --resident
+class _DecodeOnly(Dataset):
+    """what ``ResidentSet.build`` iterates: ``default_loader`` of each path and nothing else -- no transform, no random draw"""
+
+    def __init__(self, paths):
+        self.paths = list(paths)
+
+    def __getitem__(self, index):
+        return default_loader(self.paths[index])
+
+    def __len__(self):
+        return len(self.paths)
+
+
+def _as_list(items):
+    return list(items)
+
+
+class ResidentSet:
+    """A dataset decoded ONCE and held as ragged u8 ROIs (TRAIN --resident): one blob in ``dataset.images`` order, an int64 offset table
+    of n + 1 entries (the last one the blob's size), int32 heights and widths, int64 targets and the path list.  ``in_channels`` is 1
+    when every image is 2-D (grey), else 3 with the grey images replicated here, once; ``collate_rois`` decides that per BATCH, so the
+    two feeds agree for all-grey and all-RGB datasets only.  ``to_device`` uploads blob and tables once; every batch of every epoch is
+    then cut on the device by ``cut`` (ifcbk_roi_gather), which leaves the resident blob untouched -- ifcbk_roi_jitter maps the blob it
+    is given in place, so the resize kernels never get the resident one.  Data parallel: every rank holds the full set (the epoch
+    permutation is global); sharded residency is not implemented."""
+
+    def __init__(self, blob, offs, hs, ws, targets, paths, in_channels):
+        self.blob, self.offs, self.hs, self.ws, self.targets = blob, offs, hs, ws, targets
+        self.paths, self.in_channels = list(paths), int(in_channels)
+        self.dev = None                   # to_device: dict(pixels, offs, hs, ws, targets) of device tensors
+        self.ready = None                 # ... and the event recorded behind their upload
+        self.stream = None                # ... on this stream
+
+    @classmethod
+    def build(cls, dataset, loaders=0):
+        """one pass over ``dataset.images`` in their order, through a DataLoader of ``loaders`` workers over ``default_loader`` alone.
+        Touches neither ``dataset.transforms`` nor any random stream: ``__getitem__`` would call ``flip_code()``, and a DataLoader
+        draws its workers' base seed from torch's global generator unless it is handed one of its own."""
+        from torch.utils.data import DataLoader
+        paths = list(dataset.images)
+        loader = DataLoader(_DecodeOnly(paths), batch_size=64, shuffle=False, num_workers=int(loaders), collate_fn=_as_list,
+                            generator=torch.Generator())
+        imgs = [im for chunk in loader for im in chunk]
+        ch = 3 if any(im.ndim == 3 for im in imgs) else 1
+        if ch == 3:
+            imgs = [im if im.ndim == 3 else np.repeat(im[:, :, None], 3, 2) for im in imgs]
+        hs = np.array([im.shape[0] for im in imgs], np.int32)
+        ws = np.array([im.shape[1] for im in imgs], np.int32)
+        offs = np.zeros(len(imgs) + 1, np.int64)
+        np.cumsum(hs.astype(np.int64) * ws * ch, out=offs[1:])
+        blob = np.concatenate([np.ascontiguousarray(im).reshape(-1) for im in imgs]) if imgs else np.zeros(0, np.uint8)
+        return cls(blob, offs, hs, ws, np.array(dataset.targets, np.int64), paths, ch)
+
+    def __len__(self):
+        return len(self.hs)
+
+    @property
+    def nbytes(self):
+        """what ``to_device`` puts on the GPU"""
+        return int(self.blob.nbytes + self.offs.nbytes + self.hs.nbytes + self.ws.nbytes + self.targets.nbytes)
+
+    def to_device(self, device, stream):
+        """one pinned upload of the blob and the tables on ``stream``, and the ``ready`` event behind it (as ``upload_bin``)"""
+        with torch.cuda.stream(stream):
+            host = {k: torch.from_numpy(getattr(self, a)).pin_memory() for k, a in
+                    (('pixels', 'blob'), ('offs', 'offs'), ('hs', 'hs'), ('ws', 'ws'), ('targets', 'targets'))}
+            self._pinned = host           # (lives as long as the set: the copies below are asynchronous)
+            self.dev = {k: v.to(device, non_blocking=True) for k, v in host.items()}
+            self.ready = torch.cuda.Event()
+            self.ready.record(stream)
+        self.stream = stream
+        return self
+
+    def check_indices(self, idx_host):
+        """the range check ifcbk_roi_gather cannot make: on the HOST copy of the indices, before anything is launched"""
+        idx = np.asarray(idx_host, np.int64).reshape(-1)
+        if idx.size < 1 or int(idx.min()) < 0 or int(idx.max()) >= len(self):
+            raise IndexError('ResidentSet: %d indices in [%s, %s] for a set of %d ROIs' % (
+                idx.size, idx.min() if idx.size else '-', idx.max() if idx.size else '-', len(self)))
+        return idx
+
+    def cut(self, ctx, idx_dev, idx_host, stream):
+        """the compact batch of ROIs ``idx`` (``idx_dev``: int64 device tensor, ``idx_host``: its host copy) on ``stream`` through the
+        library context ``ctx``: fresh ``pixels`` / ``offs`` / ``hs`` / ``ws`` tensors, allocated through torch under the current
+        stream as an upload's are, plus the batch's own ``max_h`` / ``max_w`` and ``in_channels`` -- the first seven entries of
+        ``rois_to_device``'s result.  No host sync: sizes and maxima come from the host table."""
+        from . import _lib
+        idx = self.check_indices(idx_host)
+        n = idx.size
+        if not (torch.is_tensor(idx_dev) and idx_dev.dtype == torch.int64 and idx_dev.is_cuda and idx_dev.numel() == n and idx_dev.is_contiguous()):
+            raise ValueError('ResidentSet.cut: idx_dev is a contiguous int64 device tensor of the %d indices' % n)
+        if n > _lib.ROI_GATHER_MAX_N:
+            raise ValueError('ResidentSet.cut: %d ROIs in one batch, ifcbk_roi_gather takes %d' % (n, _lib.ROI_GATHER_MAX_N))
+        total = int((self.offs[idx + 1] - self.offs[idx]).sum())
+        d, dev = self.dev, self.dev['pixels'].device
+        pixels = torch.empty(total, dtype=torch.uint8, device=dev)
+        offs = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        hs = torch.empty(n, dtype=torch.int32, device=dev)
+        ws = torch.empty(n, dtype=torch.int32, device=dev)
+        ctx.call('ifcbk_roi_gather', _lib.ptr(d['pixels']), _lib.ptr(d['offs']), _lib.ptr(d['hs']), _lib.ptr(d['ws']), _lib.ptr(idx_dev), n,
+                 self.in_channels, _lib.ptr(pixels), total, _lib.ptr(offs), _lib.ptr(hs), _lib.ptr(ws), _lib._vp(stream.cuda_stream))
+        return dict(pixels=pixels, offs=offs[:n], hs=hs, ws=ws, max_h=int(self.hs[idx].max()), max_w=int(self.ws[idx].max()),
+                    in_channels=self.in_channels)
+
+
+def draw_items(transform, n):
+    """the per-item draws of n items in batch order, by the very calls ``NeustonDataset.__getitem__`` makes (``flip_code()``, then
+    ``jitter_factors()`` when jitter is set), as the ``flips`` / ``turn`` / ``brightness`` / ``contrast`` entries ``collate_rois`` builds
+    from such items: a ``--resident`` run and a ``--loaders 0`` run of the same command consume identical random streams."""
+    items = []
+    for _ in range(n):
+        flip = transform.flip_code() if transform is not None else 0
+        if transform is not None and getattr(transform, 'jitter', None) is not None:
+            items.append((flip, bool(getattr(transform, 'rot90', False))) + transform.jitter_factors())
+        elif transform is not None and getattr(transform, 'rot90', False):
+            items.append((flip, True))
+        else:
+            items.append((flip,))
+    out = dict(flips=torch.tensor([it[0] for it in items], dtype=torch.uint8))
+    if any(len(it) > 1 and it[1] for it in items):
+        out['turn'] = True
+    for key, k in (('brightness', 2), ('contrast', 3)):
+        if any(len(it) > k and it[k] is not None for it in items):
+            out[key] = torch.tensor([it[k] if len(it) > k and it[k] is not None else 1.0 for it in items], dtype=torch.float32)
+    return out

@@ -481,10 +481,35 @@ class NeustonModel(nn.Module):
         teacher engine's own prefetch slot; validation and RUN batches are not."""
         from .neuston_data import rois_to_device
         eng = self.model.engine
+        return self._stage(lambda side: (rois_to_device(rois, eng.dev, transform), input_classes), transform, train)
+
+    def stage_resident_batch(self, res, idx_dev, idx_host, transform=None, train=False, draws=None):
+        """TRAIN --resident: ``stage_batch`` for ROIs ``idx`` of a ``neuston_data.ResidentSet`` that lives on the device (``idx_dev``:
+        int64 device tensor, on the set's stream; ``idx_host``: its host copy).  The compact batch is cut on the prefetch stream by
+        ifcbk_roi_gather into tensors allocated fresh for this batch, as an upload's are (never per-slot buffers: with a teacher
+        attached its resize reads ``pixels`` on another stream, under ``record_stream``); the resident blob is only read, so the
+        in-place jitter maps the copy.  The per-item flip codes and jitter factors are drawn HERE, in the main process, in batch
+        order (``neuston_data.draw_items``; ``draws``: that function's result, drawn by the caller instead), the targets are gathered
+        from the resident ones, and everything behind that is ``stage_batch``'s own code."""
+        from .neuston_data import attach_draws, draw_items
+        eng = self.model.engine
+        if draws is None:
+            draws = draw_items(transform, len(idx_host))
+
+        def make(side):
+            side.wait_event(res.ready)
+            kw = attach_draws(res.cut(eng.pre_ctx, idx_dev, idx_host, side), draws, eng.dev, transform)
+            return kw, res.dev['targets'].index_select(0, idx_dev)
+        return self._stage(make, transform, train)
+
+    def _stage(self, make, transform, train):
+        """the body of ``stage_batch`` / ``stage_resident_batch``: ``make(side)``, called under the prefetch stream, puts the batch on the
+        device and returns (``load_rois`` arguments, targets or None)"""
+        eng = self.model.engine
         teach = bool(train) and self._need_teacher()
         slot, side = eng.prefetch_begin()
         with torch.cuda.stream(side):
-            kw = rois_to_device(rois, eng.dev, transform)
+            kw, input_classes = make(side)
             n = eng.load_rois(slot=slot, **kw)
             if input_classes is not None:
                 eng.tgt_bufs[slot][:n].copy_(input_classes, non_blocking=True)

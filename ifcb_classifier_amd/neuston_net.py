@@ -164,6 +164,40 @@ class ShardedLoader:
         return (len(self.indices()) + self.bs - 1) // self.bs
 
 
+class ResidentBatch:
+    """what a ``ResidentLoader`` yields in the place of a collated ROI batch: the set and the batch's indices, on the device and on the host"""
+
+    def __init__(self, res, idx_dev, idx_host):
+        self.res, self.idx_dev, self.idx_host = res, idx_dev, idx_host
+
+
+class ResidentLoader(ShardedLoader):
+    """TRAIN --resident: the same order as ``ShardedLoader`` (``indices()`` is inherited: seed, epoch, rank, world and wrap-around), but
+    nothing is decoded, collated or uploaded per batch.  ``res`` is the dataset's ``neuston_data.ResidentSet``, on the device; the
+    epoch's index vector goes up once per epoch, on the set's stream, and the batches are slices of it.  Yields
+    (ResidentBatch, targets, paths) where ``ShardedLoader`` yields (rois, targets, paths); the short last batch is the same."""
+
+    def __init__(self, dataset, res, batch_size, shuffle, rank, world, seed):
+        super().__init__(dataset, batch_size, shuffle, 0, rank, world, seed)
+        if len(res) != len(dataset):
+            raise ValueError('ResidentLoader: the resident set holds %d ROIs, the dataset %d' % (len(res), len(dataset)))
+        self.res = res
+
+    def host_batches(self):
+        """-> (the epoch's index vector, int64; the (start, stop) bounds of its batches)"""
+        idx = self.res.check_indices(self.indices())
+        return idx, [(i, min(i + self.bs, len(idx))) for i in range(0, len(idx), self.bs)]
+
+    def __iter__(self):
+        res = self.res
+        idx, bounds = self.host_batches()
+        with torch.cuda.stream(res.stream):
+            idx_dev = torch.from_numpy(idx).pin_memory().to(res.dev['pixels'].device, non_blocking=True)
+        for i0, i1 in bounds:
+            part = idx[i0:i1]
+            yield (ResidentBatch(res, idx_dev[i0:i1], part), torch.from_numpy(res.targets[part]), [res.paths[j] for j in part])
+
+
 class Trainer:
     """fit/test loops with [PL] 1.3.8's observable semantics for this driver: num_sanity_val_steps=0; per epoch
     train -> validate -> callbacks; ModelCheckpoint(monitor=val_loss, top-1); EarlyStopping(val_loss, patience)
@@ -193,6 +227,15 @@ class Trainer:
             yield cur, nxt
             cur = nxt
 
+    @staticmethod
+    def _stage(model, rois, transform, targets, train=False):
+        """stage one batch of ``fit``'s loaders: a collated batch is uploaded, a ``ResidentBatch`` (TRAIN --resident) is cut on the device"""
+        if isinstance(rois, ResidentBatch):
+            return model.stage_resident_batch(rois.res, rois.idx_dev, rois.idx_host, transform, train=train)
+        if train:
+            return model.stage_batch(rois, transform, targets, train=True)
+        return model.stage_batch(rois, transform, targets)
+
     def _allreduce(self, t):
         # the bucket exchange: one all_reduce, or reduce-scatter + all-gather (IFCBK_DP_EXCHANGE=allreduce|rsag, dp.make_exchange)
         if getattr(self, '_exchange', None) is None:
@@ -216,9 +259,9 @@ class Trainer:
             # one batch of look-ahead: upload + on-GPU preprocessing of batch k+1 run on a side stream beside step k
             n_next = None
             for (rois, targets, paths), nxt in self._lookahead(train_loader):
-                n = model.stage_batch(rois, ttf, targets, train=True) if n_next is None else n_next
+                n = self._stage(model, rois, ttf, targets, train=True) if n_next is None else n_next
                 model.use_staged()
-                n_next = model.stage_batch(nxt[0], ttf, nxt[1], train=True) if nxt is not None else None
+                n_next = self._stage(model, nxt[0], ttf, nxt[1], train=True) if nxt is not None else None
                 model.fit_current(n, self.world, self._allreduce if self.world > 1 else None)
                 global_step += 1
             model.agg_train_loss = model.epoch_train_loss()
@@ -229,9 +272,9 @@ class Trainer:
                 steps = []
                 n_next = None
                 for (rois, targets, paths), nxt in self._lookahead(val_loader):
-                    n = model.stage_batch(rois, vtf, targets) if n_next is None else n_next
+                    n = self._stage(model, rois, vtf, targets) if n_next is None else n_next
                     model.use_staged()
-                    n_next = model.stage_batch(nxt[0], vtf, nxt[1]) if nxt is not None else None
+                    n_next = self._stage(model, nxt[0], vtf, nxt[1]) if nxt is not None else None
                     probs, loss = model.eval_current(n, with_loss=True)
                     tg = targets.to(dev, non_blocking=True)
                     steps.append(dict(val_batch_loss=loss, val_outputs=probs, val_input_classes=tg, val_input_srcs=list(paths)))
@@ -407,6 +450,7 @@ def do_training(args):
     else:
         # unset: the model file and args.yml carry no distillation entry at all
         del args.distill, args.distill_alpha, args.distill_temperature
+    resident = resident_flag(args)
     dist, rank, world = _dist()
     if rank == 0:
         with open(os.path.join(args.outdir, 'training_images.list'), 'w') as f:
@@ -441,6 +485,8 @@ def do_training(args):
         classifier.attach_teacher(teacher)
         print('Distilling from {} ({}, {} classes): alpha {:g}, temperature {:g}'.format(
             args.distill, teacher.hparams.MODEL, len(teacher.hparams.classes), args.distill_alpha, args.distill_temperature))
+    if resident:
+        training_loader, validation_loader = resident_loaders(classifier, training_loader, validation_loader, args.loaders)
     eng = classifier.model.engine
     if eng.window_batch < args.batch_size:
         # --batch is per GPU as upstream (neuston_net.py:102); BatchNorm statistics are per step, so a step cannot be chunked
@@ -470,6 +516,38 @@ def do_training(args):
         print('EXPORTED:', output_path_onnx)
         onnx_export.write_classes(output_path_onnx + '.classes', args.classes)
         print('EXPORTED:', output_path_onnx + '.classes')
+
+
+def resident_flag(args):
+    """TRAIN --resident as ``do_training`` reads it: set, it stays in ``args`` (so in args.yml and the model file's hyper_parameters);
+    unset, the entry is removed and neither file carries one -- their bytes are those of a run before the flag existed"""
+    on = bool(getattr(args, 'resident', False))
+    if not on and hasattr(args, 'resident'):
+        del args.resident
+    return on
+
+
+def resident_loaders(classifier, training_loader, validation_loader, loaders):
+    """TRAIN --resident: decode both sets once, check that they fit the memory the GPU has left now that the engine (and a teacher) is
+    built, upload them on the engine's prefetch stream and return the two loaders that cut their batches there.  No fallback: sets
+    that do not fit end TRAIN.  Data parallel: every rank does all of this for the whole sets."""
+    from .neuston_data import ResidentSet
+    eng = classifier.model.engine
+    print('Decoding the Training and Validation images once (--resident)...')
+    sets = [ResidentSet.build(ld.dataset, loaders) for ld in (training_loader, validation_loader)]
+    free, _ = torch.cuda.mem_get_info(eng.dev)
+    need = sum(s.nbytes for s in sets)
+    if need > free:
+        raise SystemExit('TRAIN --resident: the training set ({:,} bytes of ROIs and tables) and the validation set ({:,} bytes) need '
+                         '{:,} bytes on the GPU, which has {:,} bytes free beside the model: train without --resident'.format(
+                             sets[0].nbytes, sets[1].nbytes, need, free))
+    stream = eng.prefetch_stream()
+    out = []
+    for s, ld in zip(sets, (training_loader, validation_loader)):
+        s.to_device(eng.dev, stream)
+        out.append(ResidentLoader(ld.dataset, s, ld.bs, ld.shuffle, ld.rank, ld.world, ld.seed))
+    print('Resident: {} + {} ROIs, {:,} bytes, {} channel(s)'.format(len(sets[0]), len(sets[1]), need, sets[0].in_channels))
+    return out
 
 
 class _ImgSource:
@@ -639,6 +717,7 @@ def argparse_nn_train(train_subparser):
     data.add_argument('--class-min', metavar='MIN', default=2, type=int, help='Exclude classes with fewer than MIN instances. Default is 2')
     data.add_argument('--class-max', metavar='MAX', default=None, type=int, help='Limit classes to a MAX number of instances.')
     data.add_argument('--swap', default=False, action='store_true', help=argparse.SUPPRESS)
+    data.add_argument('--resident', default=False, action='store_true', help='(MI355X path, additive) Decode the training and the validation images ONCE (with --loaders workers), hold them on the GPU as ragged u8 ROIs and cut every batch of every epoch there, instead of decoding, collating and uploading each batch of each epoch again. Same order, same augmentation draws and same results as "--loaders 0" for an all-grey or an all-RGB dataset (a mixed one is held as RGB throughout, where the per-batch path decides per batch). Both sets must fit the GPU\'s free memory beside the model, else TRAIN stops and names the sizes; data parallel, every rank holds both whole sets. Default (unset) reads the files every epoch')
     epochs = t.add_argument_group(title='Epoch Parameters', description=None)
     epochs.add_argument('--emax', metavar='MAX', default=60, type=int, help='Maximum number of training epochs. Default is 60')
     epochs.add_argument('--emin', metavar='MIN', default=10, type=int, help='Minimum number of training epochs. Default is 10')

@@ -360,6 +360,26 @@ IFCBK_API int ifcbk_roi_jitter(ifcbk_ctx*, const uint8_t* pixels, const int64_t*
                          int n_img, int in_channels /*1|3*/, int max_h, int max_w,
                          const float* brightness /*[n_img], nullable*/, const float* contrast /*[n_img], nullable*/,
                          uint8_t* out /* same layout as pixels; may be == pixels */, void* stream);
+/* Cut a batch from a ragged u8 dataset that lives on the device (TRAIN --resident): for k < n
+ *   dst_hs[k] = src_hs[idx[k]], dst_ws[k] = src_ws[idx[k]],
+ *   dst_offs[k] = sum over j < k of h_j * w_j * in_channels (64-bit; an entry with h < 1 or w < 1 counts 0), dst_offs[n] = the total,
+ *   the h * w * in_channels bytes at src_pixels + src_offs[idx[k]] are copied to dst_pixels + dst_offs[k]
+ * -- the compact blob and tables neuston_data.collate_rois builds, ready for ifcbk_roi_jitter (which maps its blob in place, so never
+ * the resident one) and the resize calls.  Stream-ordered, no host sync, no workspace.  Source and destination byte addresses are
+ * arbitrary and independent; offsets and products are 64-bit throughout (a resident set exceeds 4 GiB); idx may repeat.  src_* is only
+ * read.  dst_capacity is the byte count dst_pixels holds, and the copy's grid is cut from it alone, in pieces of
+ * IFCBK_ROI_GATHER_CHUNK bytes: the caller, who knows the sizes from its host copy of the table, passes the exact total (more is
+ * legal and costs idle blocks; with less the tables are complete and the blob stops at dst_capacity).  No byte at or past
+ * dst_pixels + min(dst_offs[n], dst_capacity) is written; dst_offs holds n + 1 entries.
+ * THE RANGE OF idx IS THE CALLER'S CONTRACT: every idx[k] must index the src tables; the call cannot check device data.
+ * IFCBK_EINVAL: a NULL pointer, n < 1, n > IFCBK_ROI_GATHER_MAX_N (the scan is one block), in_channels other than 1 / 3,
+ * dst_capacity < 0. */
+#define IFCBK_ROI_GATHER_MAX_N 4096
+#define IFCBK_ROI_GATHER_CHUNK 16384
+IFCBK_API int ifcbk_roi_gather(ifcbk_ctx*, const uint8_t* src_pixels, const int64_t* src_offs, const int32_t* src_hs,
+                         const int32_t* src_ws, const int64_t* idx /*[n], device*/, int n, int in_channels /*1|3*/,
+                         uint8_t* dst_pixels, int64_t dst_capacity, int64_t* dst_offs /*[n + 1]*/, int32_t* dst_hs, int32_t* dst_ws,
+                         void* stream);
 /* mix a RESIZED batch with its reverse, in place (TRAIN --mixup / --cutmix; timm's Mixup in batch mode: the partner of image n is
  * m = N - 1 - n).  x is the u8 plane [N][S][S] a grey batch is resized to (kind = IFCBK_MIX_U8; any address) or the dense tensor
  * [N][S][S][8] (kind = IFCBK_BF16 / IFCBK_F32; 16-byte aligned).  Inside the box [y0, y1) x [x0, x1) the partners' pixels are swapped
