@@ -4,81 +4,25 @@
 // than 100 times as tall as wide that shrinks in height (`vfirst` below; the 8-bit intermediate makes the order visible by
 // one level).  Such a ROI is taller than S, so a kmax == 3 batch (fast3, roi_resize3_kernel) holds none.
 //
-// Restates Pillow's ImagingResample (libImaging/Resample.c: precompute_coeffs, normalize_coeffs_8bpc,
-// ImagingResampleHorizontal_8bpc / Vertical_8bpc) -- the arithmetic behind transforms.Resize([S,S]) at
-// /root/reference/neuston_data.py:345 and :460.  The coefficient maths runs in IEEE double on the device
-// with contraction off, so the 22-bit fixed-point taps are bit-identical to the CPU's.
-#include "common.h"
+// The arithmetic -- Pillow's ImagingResample, behind transforms.Resize([S,S]) at /root/reference/neuston_data.py:345 and :460 --
+// is in roi_resample.h, shared with roi_turn.hip and roi_fit.hip: the tap maths, the two passes, the three-tap form, the float
+// stage and the stores.  This file holds the squash path's coefficient kernel, its two resize kernels (what each stages in LDS)
+// and the dispatch.
+#include "roi_resample.h"
 
 namespace {
 
-constexpr int PRECISION_BITS = 32 - 8 - 2;
-
-__device__ __forceinline__ int clip8(int v) {
-    v >>= PRECISION_BITS;
-    return v < 0 ? 0 : (v > 255 ? 255 : v);
-}
-
 // one thread per (image, axis, output index): bounds + int taps
 __global__ void roi_coeffs_kernel(const int32_t* hs, const int32_t* ws, int n_img, int S, int kmax, int32_t* tab) {
-#pragma clang fp contract(off)
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_img * 2 * S) return;
     int xx = i % S;
     int axis = (i / S) & 1;
     int img = i / (2 * S);
     int inSize = axis == 0 ? ws[img] : hs[img];
-    // table layout [image][axis][field][S] (field 0 = first input index, 1 = tap count, 2.. = taps): the resize kernel's threads
-    // (consecutive output x) read consecutive words of each field
     int32_t* row = tab + ((size_t)(img * 2 + axis) * (2 + kmax)) * S + xx;
-    const int RS_ = S;
-    double scale = (double)((float)inSize - 0.0f) / (double)S;
-    double filterscale = scale;
-    if (filterscale < 1.0) filterscale = 1.0;
-    double support = 1.0 * filterscale;              // bilinear support = 1.0
-    double center = 0.0 + ((double)xx + 0.5) * scale;
-    double ss = 1.0 / filterscale;
-    int xmin = (int)(center - support + 0.5);
-    if (xmin < 0) xmin = 0;
-    int xmax = (int)(center + support + 0.5);
-    if (xmax > inSize) xmax = inSize;
-    xmax -= xmin;
-    if (xmax > kmax) xmax = kmax;                     // cannot happen when kmax is sized from max dims
-    double ww = 0.0;
-    for (int x = 0; x < xmax; ++x) {
-        double a = ((double)(x + xmin) - center + 0.5) * ss;
-        if (a < 0.0) a = -a;
-        double w = a < 1.0 ? 1.0 - a : 0.0;
-        ww += w;
-    }
-    for (int x = 0; x < kmax; ++x) {
-        int kq = 0;
-        if (x < xmax) {
-            double a = ((double)(x + xmin) - center + 0.5) * ss;
-            if (a < 0.0) a = -a;
-            double w = a < 1.0 ? 1.0 - a : 0.0;
-            if (ww != 0.0) w = w / ww;
-            kq = w < 0.0 ? (int)(-0.5 + w * (double)(1 << PRECISION_BITS)) : (int)(0.5 + w * (double)(1 << PRECISION_BITS));
-        }
-        row[(size_t)(2 + x) * RS_] = kq;
-    }
-    row[0] = xmin;
-    row[RS_] = xmax;
+    roi_taps(inSize, S, xx, kmax, row, S);
 }
-
-struct RoiArgs {
-    const uint8_t* pixels;
-    const int64_t* offs;
-    const int32_t* hs;
-    const int32_t* ws;
-    const uint8_t* flips;
-    const int32_t* tab;
-    void* out;
-    int f32;
-    uint8_t* out_u8;
-    int n_img, S, cin, cout, kmax;
-    float mean[3], std[3], tsc[3], tsh[3];
-};
 
 // One block per (image, output row): the image's size / offset and the row's vertical taps are block-uniform (scalar loads), a
 // thread's dependent chain is table -> pixels -> store.  As one flat grid of output pixels every thread first had to derive
@@ -99,6 +43,12 @@ __global__ __launch_bounds__(320) void roi_resize_kernel(RoiArgs a) {
     const int32_t* th = a.tab + ((size_t)(img * 2 + 0) * (2 + a.kmax)) * a.S + x;
     const int32_t* tv = a.tab + ((size_t)(img * 2 + 1) * (2 + a.kmax)) * a.S + y;
     const int xmin = th[0], xn = th[TS], ymin = tv[0], yn = tv[TS];
+    // byte offset of pixel (row, col) of the flipped ROI (channel 0)
+    auto at = [&](int row, int col) -> size_t {
+        if (vflip) row = h - 1 - row;
+        if (hflip) col = w - 1 - col;
+        return (size_t)row * w + col;
+    };
     int res[3];
     // Fast path (grey ROIs no larger than the output: at most three taps per axis, the whole batch of the benchmark): the up to
     // three source rows of this output row are brought to LDS once with coalesced byte loads -- 3 vector-memory loads per thread
@@ -117,16 +67,8 @@ __global__ __launch_bounds__(320) void roi_resize_kernel(RoiArgs a) {
             if ((int)threadIdx.x < w) srow[j][threadIdx.x] = src[(size_t)row * w + threadIdx.x];
         }
         __syncthreads();
-        const int t0 = th[2 * TS], t1 = th[3 * TS], t2 = th[4 * TS];
-        int c0 = xmin, c1 = xmin + (xn > 1 ? 1 : 0), c2 = xmin + (xn > 2 ? 2 : xn - 1);
-        if (hflip) { c0 = w - 1 - c0; c1 = w - 1 - c1; c2 = w - 1 - c2; }
-        int accv = 1 << (PRECISION_BITS - 1);
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const int acch = (1 << (PRECISION_BITS - 1)) + (int)srow[j][c0] * t0 + (int)srow[j][c1] * t1 + (int)srow[j][c2] * t2;
-            accv += clip8(acch) * tv[(2 + j) * TS];
-        }
-        res[0] = clip8(accv);
+        const int tv3[3] = {tv[2 * TS], tv[3 * TS], tv[4 * TS]};
+        res[0] = three_tap(srow[0], srow[1], srow[2], tv3, tap3_load(th, TS, hflip, w));
     } else if (lds_ok) {
         for (int j = 0; j < yn; ++j) {
             int row = ymin + j;
@@ -134,88 +76,14 @@ __global__ __launch_bounds__(320) void roi_resize_kernel(RoiArgs a) {
             for (int c = threadIdx.x; c < w; c += blockDim.x) srow[j][c] = src[(size_t)row * w + c];
         }
         __syncthreads();
-        if (vfirst) {
-            int acch = 1 << (PRECISION_BITS - 1);
-            for (int k = 0; k < xn; ++k) {
-                int col = xmin + k;
-                if (hflip) col = w - 1 - col;
-                int accv = 1 << (PRECISION_BITS - 1);
-                for (int j = 0; j < yn; ++j) accv += (int)srow[j][col] * tv[(size_t)(2 + j) * TS];
-                acch += clip8(accv) * th[(size_t)(2 + k) * TS];
-            }
-            res[0] = clip8(acch);
-        } else {
-            int accv = 1 << (PRECISION_BITS - 1);
-            for (int j = 0; j < yn; ++j) {
-                int acch = 1 << (PRECISION_BITS - 1);
-                for (int k = 0; k < xn; ++k) {
-                    int col = xmin + k;
-                    if (hflip) col = w - 1 - col;
-                    acch += (int)srow[j][col] * th[(size_t)(2 + k) * TS];
-                }
-                accv += clip8(acch) * tv[(size_t)(2 + j) * TS];
-            }
-            res[0] = clip8(accv);
-        }
+        res[0] = two_pass([&](int j, int k) { return (int)srow[j][hflip ? w - 1 - (xmin + k) : xmin + k]; }, th, xn, tv, yn, TS, vfirst);
     } else
     for (int c = 0; c < a.cin; ++c) {
-        if (vfirst) {
-            int acch = 1 << (PRECISION_BITS - 1);
-            for (int k = 0; k < xn; ++k) {
-                int col = xmin + k;
-                if (hflip) col = w - 1 - col;
-                int accv = 1 << (PRECISION_BITS - 1);
-                for (int j = 0; j < yn; ++j) {
-                    int row = ymin + j;
-                    if (vflip) row = h - 1 - row;
-                    accv += (int)src[((size_t)row * w + col) * a.cin + c] * tv[(size_t)(2 + j) * TS];
-                }
-                acch += clip8(accv) * th[(size_t)(2 + k) * TS];
-            }
-            res[c] = clip8(acch);
-            continue;
-        }
-        int accv = 1 << (PRECISION_BITS - 1);
-        for (int j = 0; j < yn; ++j) {
-            int row = ymin + j;
-            if (vflip) row = h - 1 - row;
-            int acch = 1 << (PRECISION_BITS - 1);
-            for (int k = 0; k < xn; ++k) {
-                int col = xmin + k;
-                if (hflip) col = w - 1 - col;
-                acch += (int)src[((size_t)row * w + col) * a.cin + c] * th[(size_t)(2 + k) * TS];
-            }
-            accv += clip8(acch) * tv[(size_t)(2 + j) * TS];
-        }
-        res[c] = clip8(accv);
+        res[c] = two_pass([&](int j, int k) { return (int)src[at(ymin + j, xmin + k) * a.cin + c]; }, th, xn, tv, yn, TS, vfirst);
     }
     if (!live) return;
     if (a.cin == 1) res[1] = res[2] = res[0];
-    if (a.out_u8)
-        for (int c = 0; c < a.cin; ++c) a.out_u8[i * a.cin + c] = (uint8_t)res[c];
-    if (a.out) {
-        for (int c0 = 0; c0 < a.cout; c0 += 8) {
-            float f[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                int c = c0 + j;
-                float v = 0.f;
-                if (c < 3) {
-                    v = (float)res[c] / 255.0f;
-                    v = (v - a.mean[c]) / a.std[c];
-                    v = v * a.tsc[c] + a.tsh[c];
-                }
-                f[j] = v;
-            }
-            if (a.f32) {
-                float* o = (float*)a.out + i * a.cout + c0;
-                *reinterpret_cast<float4*>(o) = make_float4(f[0], f[1], f[2], f[3]);
-                *reinterpret_cast<float4*>(o + 4) = make_float4(f[4], f[5], f[6], f[7]);
-            } else {
-                *reinterpret_cast<uint4*>((bf16_t*)a.out + i * a.cout + c0) = pack8(f);
-            }
-        }
-    }
+    ROI_STORE_PIXEL(a, i, a.cin, res[c]);
 }
 
 // The benchmark's case as its own kernel -- grey ROIs no larger than the output (three taps per axis): one block per RPB consecutive
@@ -257,6 +125,8 @@ __global__ __launch_bounds__(320) void roi_resize3_kernel(RoiArgs a) {
             for (int xx = (int)threadIdx.x; xx < wl; xx += (int)blockDim.x) srow[r][j][xx] = src[(size_t)row * w + xx];
         }
     }
+    // The three-tap arithmetic stands here and not as roi_resample.h's three_tap: this is the benchmark's kernel, and through the
+    // function it came out with 32 VGPRs for 24; as written its device code is the one it had before the header.
     const int xmin = th[0], xn = th[TS];
     const int t0 = th[2 * TS], t1 = th[3 * TS], t2 = th[4 * TS];
     int c0 = xmin, c1 = xmin + (xn > 1 ? 1 : 0), c2 = xmin + (xn > 2 ? 2 : xn - 1);
@@ -275,32 +145,8 @@ __global__ __launch_bounds__(320) void roi_resize3_kernel(RoiArgs a) {
             const int acch = (1 << (PRECISION_BITS - 1)) + (int)srow[r][j][c0] * t0 + (int)srow[r][j][c1] * t1 + (int)srow[r][j][c2] * t2;
             accv += clip8(acch) * tvv[r][j];
         }
-        const int res = clip8(accv);
-        const int64_t i = ((int64_t)img * a.S + (y0 + r)) * a.S + x;
-        if (a.out_u8) a.out_u8[i] = (uint8_t)res;
-        if (a.out) {
-            for (int cc = 0; cc < a.cout; cc += 8) {
-                float f[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const int c = cc + j;
-                    float v = 0.f;
-                    if (c < 3) {
-                        v = (float)res / 255.0f;
-                        v = (v - a.mean[c]) / a.std[c];
-                        v = v * a.tsc[c] + a.tsh[c];
-                    }
-                    f[j] = v;
-                }
-                if (a.f32) {
-                    float* o = (float*)a.out + i * a.cout + cc;
-                    *reinterpret_cast<float4*>(o) = make_float4(f[0], f[1], f[2], f[3]);
-                    *reinterpret_cast<float4*>(o + 4) = make_float4(f[4], f[5], f[6], f[7]);
-                } else {
-                    *reinterpret_cast<uint4*>((bf16_t*)a.out + i * a.cout + cc) = pack8(f);
-                }
-            }
-        }
+        const int v = clip8(accv);
+        ROI_STORE_PIXEL(a, ((int64_t)img * a.S + (y0 + r)) * a.S + x, 1, v);
     }
 }
 
@@ -336,10 +182,9 @@ extern "C" int ifcbk_roi_preprocess(ifcbk_ctx* ctx, const ifcbk_roi_desc* d, con
     IFCBK_LAUNCH_CHECK(ctx, "roi_coeffs");
     RoiArgs a;
     a.pixels = pixels; a.offs = offs; a.hs = hs; a.ws = ws; a.flips = d->flip_bits_valid ? flips : nullptr;
-    a.tab = (const int32_t*)ctx->ws; a.out = out; a.f32 = d->dtype == IFCBK_F32; a.out_u8 = out_u8;
-    a.n_img = d->n_img; a.S = d->S; a.cin = d->in_channels; a.cout = d->out_channels; a.kmax = kmax;
-    for (int i = 0; i < 3; ++i) { a.mean[i] = d->mean[i]; a.std[i] = d->std[i]; a.tsc[i] = d->tin_scale[i]; a.tsh[i] = d->tin_shift[i]; }
-    const int bx = d->S <= 64 ? 64 : d->S <= 128 ? 128 : d->S <= 192 ? 192 : d->S <= 256 ? 256 : 320;      // threads per output row
+    a.tab = (const int32_t*)ctx->ws; a.out = out; a.out_u8 = out_u8;
+    roi_args_desc(a, d, kmax);
+    const int bx = roi_row_threads(d->S);
     if (d->in_channels == 1 && kmax == 3 && d->S <= 320)      // (kmax == 3: no ROI is larger than the output, so w <= S <= 320 threads)
         hipLaunchKernelGGL(roi_resize3_kernel, dim3((unsigned)(d->n_img * cdiv(d->S, RPB))), dim3(bx), 0, st, a);
     else

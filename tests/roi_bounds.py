@@ -5,7 +5,7 @@ A plain helper module like conv_bounds.py / op_bounds.py.  Everything here runs 
 
 Paths.  ifcbk_roi_preprocess picks the kernel from the BATCH (in_channels, S, and kmax, which comes from the caller's max_h / max_w),
 roi_resize_kernel then picks its arithmetic per ROI.  PATHS restates those conditions on the host; each entry quotes the source
-line it mirrors, and the CPU test asserts that line is still in roi.hip.
+line it mirrors, and the CPU test asserts that line is still in roi.hip (QUOTED_SHARED: in roi_resample.h).
 
 u8 plane.  Expected: oracle.pil_resize.resize_bilinear_u8 of the flipped ROI (the CPU twin proves it equal to Pillow for every shape
 of the table).  Equality, no tolerance.
@@ -37,7 +37,7 @@ def kmax_for(max_h, max_w, S):
 
 
 def block_x(S):
-    """roi.hip: `const int bx = ...` (threads per output row)"""
+    """roi_resample.h: roi_row_threads (threads per output row)"""
     return 64 if S <= 64 else 128 if S <= 128 else 192 if S <= 192 else 256 if S <= 256 else 320
 
 
@@ -67,8 +67,11 @@ PATHS = {
 }
 # further source text the predicates rely on (constants and the pass-order rule)
 QUOTED = ('constexpr int LR = 5, LW = 640;', 'constexpr int RPB = 8;', 'return (int)ceil(scale) * 2 + 1;',
-          'const int bx = d->S <= 64 ? 64 : d->S <= 128 ? 128 : d->S <= 192 ? 192 : d->S <= 256 ? 256 : 320;',
-          'const bool vfirst = h > 100 * w && h > a.S;')
+          'const int bx = roi_row_threads(d->S);', 'const bool vfirst = h > 100 * w && h > a.S;')
+# source text of csrc/roi_resample.h, the resampler the three kernel sets share: the threads-per-row ladder (block_x), and the
+# constants and the column clamp of the band staging that roi_turn_cases.py and roi_fit_cases.py rely on
+QUOTED_SHARED = ('inline int roi_row_threads(int S) { return S <= 64 ? 64 : S <= 128 ? 128 : S <= 192 ? 192 : S <= 256 ? 256 : 320; }',
+                 'constexpr int BAND_RPB = 8, BAND_ROWS = 12, BAND_PITCH = 324;', 'const int wl = wt < 320 ? wt : 320;')
 
 
 def _small(S):

@@ -106,10 +106,11 @@ PATHS = {
                              'hipLaunchKernelGGL(roi_fit_setup_kernel, dim3((unsigned)d->n_img), dim3(256), 0, st, pixels, offs, hs, ws, cd, codemask, '
                              'max_h, max_w, d->S, d->in_channels, kmax, fill, meta, tab);'),
 }
-# further source text the predicates, the case table and the workspace formula rely on
-QUOTED = ('constexpr int FLR = 5, FLW = 640;', 'constexpr int FRPB = 8, FBAND = 12, FLP = 324;', 'constexpr int FIT_META = 16;',
+# further source text the predicates, the case table and the workspace formula rely on (with roi_bounds.QUOTED_SHARED, looked up in
+# roi_resample.h)
+QUOTED = ('constexpr int FLR = 5, FLW = 640;', '__shared__ uint8_t strip[BAND_ROWS][BAND_PITCH];', 'constexpr int FIT_META = 16;',
           'const int ht = turned ? w : h, wt = turned ? h : w;', 'const bool vfirst = (int64_t)ht > 100 * (int64_t)wt && nh < ht;',
-          'const int fbx = d->S <= 64 ? 64 : d->S <= 128 ? 128 : d->S <= 192 ? 192 : d->S <= 256 ? 256 : 320;',
+          'const int fbx = roi_row_threads(d->S);',
           'return (size_t)d->n_img * FIT_META * sizeof(int32_t) + (size_t)d->n_img * 2 * d->S * (2 + kmax) * sizeof(int32_t);',
           'if (fill < -1 || fill > 255) IFCBK_FAIL(ctx, IFCBK_EINVAL,')
 QUOTED_DIMS = ('if (m <= S) return 3;', 'int64_t c = (3 * m + 2 * (int64_t)S - 1) / (2 * (int64_t)S);', 'return (int)c * 2 + 1;',

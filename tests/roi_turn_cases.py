@@ -47,11 +47,10 @@ PATHS = {
     'roi_turn_coeffs_kernel': (lambda cin, S, kmax, ht, wt: True,
                                'hipLaunchKernelGGL(roi_turn_coeffs_kernel, dim3(cdiv(nco, 256)), dim3(256), 0, st, hs, ws, flips, d->n_img, d->S, kmax, (int32_t*)ctx->ws);'),
 }
-# further source text the predicates and the case table rely on
-QUOTED = ('constexpr int TLR = 5, TLW = 640;', 'constexpr int TRPB = 8, TBAND = 12, TLP = 324;',
+# further source text the predicates and the case table rely on (with roi_bounds.QUOTED_SHARED, looked up in roi_resample.h)
+QUOTED = ('constexpr int TLR = 5, TLW = 640;', '__shared__ uint8_t strip[BAND_ROWS][BAND_PITCH];',
           'const int ht = turned ? w : h, wt = turned ? h : w;', 'const bool vfirst = ht > 100 * wt && ht > a.S;',
-          'int inSize = (axis == 0) != turned ? ws[img] : hs[img];', 'const int wl = wt < 320 ? wt : 320;',
-          'const int tbx = d->S <= 64 ? 64 : d->S <= 128 ? 128 : d->S <= 192 ? 192 : d->S <= 256 ? 256 : 320;')
+          'int inSize = (axis == 0) != turned ? ws[img] : hs[img];', 'const int tbx = roi_row_threads(d->S);')
 # roi.hip: the only way into roi_turn.hip
 BRANCH = 'if (d->flip_bits_valid == 2)'
 

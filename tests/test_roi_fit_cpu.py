@@ -138,6 +138,9 @@ def test_fit_path_predicates_quote_the_source_and_every_path_is_reached():
         assert _norm(cond) in src, '%s: %r is no longer in roi_fit.hip' % (name, cond)
     for q in fc.QUOTED:
         assert _norm(q) in src, q
+    shared = _norm(open(os.path.join(CSRC, 'roi_resample.h')).read())
+    for q in fc.tc.rb.QUOTED_SHARED:
+        assert _norm(q) in shared, q
     dims = _norm(open(os.path.join(CSRC, 'roi_fit_dims.h')).read())
     for q in fc.QUOTED_DIMS:
         assert _norm(q) in dims, q
@@ -202,7 +205,7 @@ def test_tap_bound_holds_where_the_squash_bound_does_not():
 
 
 def test_band_of_a_row_block_fits_the_strip_for_every_enlarging_axis():
-    """roi_fit_resize3_kernel stages, per block of FRPB = 8 output rows, at most FBAND = 12 rows: 8 consecutive inner rows of an axis that
+    """roi_fit_resize3_kernel stages, per block of BAND_RPB = 8 output rows, at most BAND_ROWS = 12 rows: 8 consecutive inner rows of an axis that
     does not shrink (input size <= inner size <= S) span at most 10 input rows"""
     for S in (299, 40):
         for n_out in sorted({S, S - 1, S // 2, S // 3, 7, 2, 1}):

@@ -15,6 +15,7 @@ from oracle import pil_resize as PR
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, 'tests', 'golden')
+CSRC = os.path.join(ROOT, 'ifcb_classifier_amd', 'csrc')
 Image = pytest.importorskip('PIL.Image')
 
 
@@ -95,11 +96,14 @@ def test_pass_order_rule_on_the_committed_boundary_and_goldens():
 
 
 def test_path_predicates_quote_the_source_and_every_path_has_cases():
-    src = _norm(open(os.path.join(ROOT, 'ifcb_classifier_amd', 'csrc', 'roi.hip')).read())
+    src = _norm(open(os.path.join(CSRC, 'roi.hip')).read())
     for name, (pred, cond) in rb.PATHS.items():
         assert _norm(cond) in src, '%s: %r is no longer in roi.hip' % (name, cond)
     for q in rb.QUOTED:
         assert _norm(q) in src, q
+    shared = _norm(open(os.path.join(CSRC, 'roi_resample.h')).read())
+    for q in rb.QUOTED_SHARED:
+        assert _norm(q) in shared, q
     reached = {p: [set(), set()] for p in rb.PATHS}           # path -> [flip codes seen, (flipped, not flipped)]
     vfirst = set()
     for c in rb.ROI:
@@ -137,13 +141,27 @@ def test_path_predicates_quote_the_source_and_every_path_has_cases():
 
 def test_workspace_formula_covers_the_coefficient_table():
     """roi_coeffs_kernel writes fields 0 .. 1 + kmax of [image][axis][field][S]: the last word is index n * 2 * (2 + kmax) * S - 1"""
-    src = _norm(open(os.path.join(ROOT, 'ifcb_classifier_amd', 'csrc', 'roi.hip')).read())
+    src = _norm(open(os.path.join(CSRC, 'roi.hip')).read())
     for q in ('return (size_t)d->n_img * 2 * d->S * (2 + kmax) * sizeof(int32_t);', 'if (i >= n_img * 2 * S) return;',
-              'int32_t* row = tab + ((size_t)(img * 2 + axis) * (2 + kmax)) * S + xx;', 'row[(size_t)(2 + x) * RS_] = kq;', 'for (int x = 0; x < kmax; ++x) {'):
+              'int32_t* row = tab + ((size_t)(img * 2 + axis) * (2 + kmax)) * S + xx;', 'roi_taps(inSize, S, xx, kmax, row, S);'):
         assert _norm(q) in src, q
+    shared = _norm(open(os.path.join(CSRC, 'roi_resample.h')).read())           # roi_taps: the writes behind `row`
+    for q in ('row[(size_t)(2 + x) * fieldStride] = kq;', 'for (int x = 0; x < kmax; ++x) {', 'row[0] = xmin;', 'row[fieldStride] = xmax;'):
+        assert _norm(q) in shared, q
     n, S, k = 5, 299, 7
     last = ((n - 1) * 2 + 1) * (2 + k) * S + (S - 1) + (2 + k - 1) * S
     assert last == n * 2 * S * (2 + k) - 1
+
+
+def test_the_resampler_arithmetic_is_written_once():
+    """the tap rounding and the float stage's division stand once under csrc/ (roi_resample.h): a resize feature that pastes a
+    further copy instead of calling the shared one fails here"""
+    text = {f: open(os.path.join(CSRC, f)).read() for f in sorted(os.listdir(CSRC)) if f.endswith(('.hip', '.h'))}
+    assert len(text) > 20 and 'roi_resample.h' in text
+    rounding = r'\(int\)\s*\(\s*0\.5\s*\+\s*\w+\s*\*\s*\(double\)\s*\(\s*1\s*<<\s*PRECISION_BITS\s*\)\s*\)'
+    for what, pat in (('tap rounding', rounding), ('float stage', r'/\s*255\.0f')):
+        hits = [f for f, t in text.items() for _ in re.finditer(pat, t)]
+        assert hits == ['roi_resample.h'], '%s: %s' % (what, hits)
 
 
 # ---------------------------------------------------------------------------------------------- the checkers can fail

@@ -73,6 +73,9 @@ def test_turn_path_predicates_quote_the_source_and_every_path_is_reached_turned_
         assert _norm(cond) in src, '%s: %r is no longer in roi_turn.hip' % (name, cond)
     for q in tc.QUOTED:
         assert _norm(q) in src, q
+    shared = _norm(open(os.path.join(ROOT, 'ifcb_classifier_amd', 'csrc', 'roi_resample.h')).read())
+    for q in tc.rb.QUOTED_SHARED:
+        assert _norm(q) in shared, q
     assert _norm(tc.BRANCH) in _norm(open(os.path.join(ROOT, 'ifcb_classifier_amd', 'csrc', 'roi.hip')).read())
     reached = {p: set() for p in tc.PATHS}
     vf = set()
@@ -116,7 +119,7 @@ def test_turn_path_predicates_quote_the_source_and_every_path_is_reached_turned_
 
 
 def test_band_of_a_row_block_fits_the_strip():
-    """roi_turn_resize3_kernel stages, per block of TRPB = 8 output rows, rows first .. last of the turned image, at most TBAND = 12
+    """roi_turn_resize3_kernel stages, per block of BAND_RPB = 8 output rows, rows first .. last of the turned image, at most BAND_ROWS = 12
     of them: for every input size <= S the 8 rows' windows span at most 10 rows"""
     for S in (299, 224, 40, 320):
         for size in range(1, S + 1):
