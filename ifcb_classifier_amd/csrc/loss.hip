@@ -5,14 +5,16 @@
 // softmax_xent_mix_kernel, two targets per image, with or without class weights and smoothing), or a teacher's logits (TRAIN --distill:
 // softmax_xent_distill_kernel, with or without class weights and smoothing).
 #include "common.h"
+#include "loss_rows.h"
 #include <float.h>
 #include <math.h>
 
 namespace {
 
-// softmax_xent_kernel's shape -- one 1024-thread block, 4 lanes per sample (classes j = sub, sub+4, ...), fixed butterflies, fixed-order
-// final sum: bitwise reproducible -- behind a pre-pass for the normaliser W = sum_n w[t_n]: per-slot partial sums in LDS (slot s takes
-// the samples s, s + 256, ... in order), summed in slot order by thread 0 and broadcast.
+// Every kernel below has the shape loss_rows.h states (one 1024-thread block, four lanes per sample, fixed butterflies, fixed-order slot
+// sums: bitwise reproducible) and is built from its pieces; a kernel's comment gives its own formulas and the notes on its arithmetic.
+
+// softmax_xent_kernel behind a pre-pass for the normaliser W = sum_n w[t_n] (a slot sum, broadcast):
 //   c_n = weight * (w[t_n] / W),   d[n][j] = c_n * (p[n][j] - onehot),   loss = (sum_slots sum_n w[t_n] l_n) * (1 / W) * weight
 // With all-ones class weights W == N exactly (a sum of ones below 2^24) and 1 / W == 1.f / N, so every operation has the operands
 // it has in softmax_xent_kernel: loss and dlogits are then bit-equal to the unweighted kernel's.
@@ -20,36 +22,21 @@ namespace {
 __global__ __launch_bounds__(1024) void softmax_xent_w_kernel(const float* logits, const int64_t* target, const float* class_weight,
                                                               int N, int NC, float weight, float* loss_out, int loss_acc,
                                                               float* dlogits) {
-    __shared__ float sl[256];
+    __shared__ float sl[LOSS_SLOTS];
     __shared__ float sW;
-    const int sub = threadIdx.x & 3, slot = threadIdx.x >> 2;
-    if (sub == 0) {
-        float wsum = 0.f;
+    const int sub = loss_sub(), slot = loss_slot();
+    float wsum = 0.f;
+    if (sub == 0)
         for (int n = slot; n < N; n += 256) wsum += class_weight[(int)target[n]];
-        sl[slot] = wsum;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float s = 0.f;
-        for (int i = 0; i < 256; ++i) s += sl[i];
-        sW = s;
-    }
-    __syncthreads();
-    const float W = sW;
+    const float W = slot_sum(sl, &sW, wsum);
     const float invW = 1.f / W;
     float local = 0.f;
     for (int n0 = 0; n0 < N; n0 += 256) {
         const int n = n0 + slot;
         const bool ok = n < N;
         const float* l = logits + (size_t)(ok ? n : 0) * NC;
-        float mx = -INFINITY;
-        for (int j = sub; j < NC; j += 4) mx = fmaxf(mx, l[j]);
-        mx = fmaxf(mx, __shfl_xor(mx, 1));
-        mx = fmaxf(mx, __shfl_xor(mx, 2));
-        float s = 0.f;
-        for (int j = sub; j < NC; j += 4) s += expf(l[j] - mx);
-        s += __shfl_xor(s, 1);
-        s += __shfl_xor(s, 2);
+        const float mx = row_max(l, NC, sub);
+        const float s = row_expsum(l, mx, NC, sub);
         const int tg = ok ? (int)target[n] : 0;
         const float wt = ok ? class_weight[tg] : 0.f;
         if (ok && sub == 0) {
@@ -64,52 +51,33 @@ __global__ __launch_bounds__(1024) void softmax_xent_w_kernel(const float* logit
         }
     }
     __syncthreads();                       // (thread 0 has finished reading the W partials)
-    if (sub == 0) sl[slot] = local;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float s = 0.f;
-        for (int i = 0; i < 256; ++i) s += sl[i];
-        s = s * invW * weight;
-        loss_out[0] = loss_acc ? loss_out[0] + s : s;
-    }
+    const float total = slot_sum0(sl, local);
+    if (threadIdx.x == 0) loss_store(loss_out, loss_acc, total * invW * weight);
 }
 
 // Label-smoothed cross-entropy: nn.CrossEntropyLoss(weight=w, label_smoothing=eps), mean reduction (TRAIN --label-smoothing).  With C = NC,
 // p = softmax(l), w = class_weight (NULL: all ones), W = sum_n w[t_n], SW = sum_k w[k], c1 = 1 - eps, eC = eps / C:
 //   loss      = weight / W * sum_n [ c1 w[t_n] (-log p[n][t_n]) + eC sum_j w[j] (-log p[n][j]) ]
 //   d[n][j]   = weight / W * [ (c1 w[t_n] + eC SW) p[n][j] - c1 w[t_n] [j == t_n] - eC w[j] ]
-// The normaliser stays W (torch does not rescale it by eps).  softmax_xent_w_kernel's shape: one 1024-thread block, 4 lanes per sample,
-// fixed butterflies, fixed-order slot sums; W and SW come from one pre-pass (slot s takes the samples / classes s, s + 256, ... in
-// order; thread 0 sums the 256 partials of each in slot order and broadcasts) -- bitwise reproducible.  The smoothing term is summed as
-// the non-negative pieces w[j] * ((mx - l[j]) + log s): mx >= l[j], and s >= 1 because the row's maximum contributes expf(0) == 1 to a sum
-// of non-negative terms; sum w * lse - sum w * l would cancel.  Per sample: 2 NC expf and one logf as in the kernels above, and for the
-// smoothing NC (subtract, add, multiply-add) + 2 butterfly adds for the loss, NC (multiply, multiply-subtract) for dlogits.
+// The normaliser stays W (torch does not rescale it by eps).  W and SW come from one pre-pass (slot s takes the samples / classes
+// s, s + 256, ... in order).  The smoothing term is smooth_q's sum of non-negative pieces.  Per sample: 2 NC expf and one logf as in the
+// kernels above, and for the smoothing NC (subtract, add, multiply-add) + 2 butterfly adds for the loss, NC (multiply, multiply-subtract)
+// for dlogits.
 // eps == 0 computes softmax_xent_w's function through this kernel's own operations (not bit-equal to it).
 // A target outside [0, NC) is the caller's fault, as there; so is W == 0 (every target in a zero-weight class: torch gives NaN too).
 __global__ __launch_bounds__(1024) void softmax_xent_ls_kernel(const float* logits, const int64_t* target, const float* class_weight,
                                                                int N, int NC, float weight, float eps, float* loss_out, int loss_acc,
                                                                float* dlogits) {
-    __shared__ float sl[256];
-    __shared__ float sk[256];
+    __shared__ float sl[2][LOSS_SLOTS];
     __shared__ float sW[2];
-    const int sub = threadIdx.x & 3, slot = threadIdx.x >> 2;
+    const int sub = loss_sub(), slot = loss_slot();
+    float wsum = 0.f, ksum = 0.f;
     if (sub == 0) {
-        float wsum = 0.f, ksum = 0.f;
-        for (int n = slot; n < N; n += 256) wsum += class_weight ? class_weight[(int)target[n]] : 1.f;
-        for (int k = slot; k < NC; k += 256) ksum += class_weight ? class_weight[k] : 1.f;
-        sl[slot] = wsum;
-        sk[slot] = ksum;
+        for (int n = slot; n < N; n += 256) wsum += class_w(class_weight, (int)target[n]);
+        for (int k = slot; k < NC; k += 256) ksum += class_w(class_weight, k);
     }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float s = 0.f, k = 0.f;
-        for (int i = 0; i < 256; ++i) s += sl[i];
-        for (int i = 0; i < 256; ++i) k += sk[i];
-        sW[0] = s;
-        sW[1] = k;
-    }
-    __syncthreads();
-    const float W = sW[0], SW = sW[1];
+    const float2 sums = slot_sum2(sl, sW, wsum, ksum);
+    const float W = sums.x, SW = sums.y;
     const float invW = 1.f / W;
     const float g = weight / W;
     const float c1 = 1.f - eps, eC = eps / (float)NC;
@@ -118,21 +86,12 @@ __global__ __launch_bounds__(1024) void softmax_xent_ls_kernel(const float* logi
         const int n = n0 + slot;
         const bool ok = n < N;
         const float* l = logits + (size_t)(ok ? n : 0) * NC;
-        float mx = -INFINITY;
-        for (int j = sub; j < NC; j += 4) mx = fmaxf(mx, l[j]);
-        mx = fmaxf(mx, __shfl_xor(mx, 1));
-        mx = fmaxf(mx, __shfl_xor(mx, 2));
-        float s = 0.f;
-        for (int j = sub; j < NC; j += 4) s += expf(l[j] - mx);
-        s += __shfl_xor(s, 1);
-        s += __shfl_xor(s, 2);
+        const float mx = row_max(l, NC, sub);
+        const float s = row_expsum(l, mx, NC, sub);
         const float ls = logf(s);
-        float q = 0.f;
-        for (int j = sub; j < NC; j += 4) q += (class_weight ? class_weight[j] : 1.f) * ((mx - l[j]) + ls);
-        q += __shfl_xor(q, 1);
-        q += __shfl_xor(q, 2);
+        const float q = smooth_q(l, class_weight, mx, ls, NC, sub);
         const int tg = ok ? (int)target[n] : 0;
-        const float wt = ok ? (class_weight ? class_weight[tg] : 1.f) : 0.f;
+        const float wt = ok ? class_w(class_weight, tg) : 0.f;
         const float hard = c1 * wt;
         if (ok && sub == 0) {
             const float li = mx + ls - l[tg];
@@ -143,18 +102,12 @@ __global__ __launch_bounds__(1024) void softmax_xent_ls_kernel(const float* logi
             const float is = 1.f / s;
             const float A = hard + eC * SW;
             for (int j = sub; j < NC; j += 4)
-                d[j] = g * (A * (expf(l[j] - mx) * is) - (j == tg ? hard : 0.f) - eC * (class_weight ? class_weight[j] : 1.f));
+                d[j] = smooth_dlogit(g, A, expf(l[j] - mx) * is, j == tg ? hard : 0.f, eC, class_w(class_weight, j));
         }
     }
     __syncthreads();                       // (thread 0 has finished reading the pre-pass partials)
-    if (sub == 0) sl[slot] = local;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float s = 0.f;
-        for (int i = 0; i < 256; ++i) s += sl[i];
-        s = s * invW * weight;
-        loss_out[0] = loss_acc ? loss_out[0] + s : s;
-    }
+    const float total = slot_sum0(sl[0], local);
+    if (threadIdx.x == 0) loss_store(loss_out, loss_acc, total * invW * weight);
 }
 
 // Focal loss (TRAIN --focal-gamma): with p = softmax(l), w = class_weight (NULL: all ones), W = sum_n w[t_n], g = gamma >= 0,
@@ -162,8 +115,7 @@ __global__ __launch_bounds__(1024) void softmax_xent_ls_kernel(const float* logi
 //   loss    = weight / W * sum_n w[t_n] u_n^g L_n
 //   d[n][j] = weight / W * w[t_n] (p[n][j] - [j == t_n]) (u_n^g + g p[n][t_n] u_n^(g-1) L_n)
 // The normaliser stays W, so g -> 0 is softmax_xent_w's function and the class weights are focal loss's per-class alpha.
-// softmax_xent_ls_kernel's shape: one 1024-thread block, 4 lanes per sample, fixed butterflies, fixed-order slot sums, one pre-pass for W
-// -- bitwise reproducible.  Three points of the arithmetic:
+// One pre-pass for W.  Three points of the arithmetic:
 //   u is so / s with so = sum_{j != t} expf(l_j - mx), the sum s with the target's term left out: non-negative terms, no cancellation
 //     (1 - p_t and s - e_t cancel when the target is the row's maximum: e_t == 1).  Term by term so's chain is below s's, so u <= 1.
 //     The target's dlogits element is -u, not p_t - 1, for the same reason.
@@ -178,22 +130,13 @@ __global__ __launch_bounds__(1024) void softmax_xent_ls_kernel(const float* logi
 __global__ __launch_bounds__(1024) void softmax_xent_focal_kernel(const float* logits, const int64_t* target, const float* class_weight,
                                                                   int N, int NC, float weight, float gam, float* loss_out, int loss_acc,
                                                                   float* dlogits) {
-    __shared__ float sl[256];
+    __shared__ float sl[LOSS_SLOTS];
     __shared__ float sW;
-    const int sub = threadIdx.x & 3, slot = threadIdx.x >> 2;
-    if (sub == 0) {
-        float wsum = 0.f;
-        for (int n = slot; n < N; n += 256) wsum += class_weight ? class_weight[(int)target[n]] : 1.f;
-        sl[slot] = wsum;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float s = 0.f;
-        for (int i = 0; i < 256; ++i) s += sl[i];
-        sW = s;
-    }
-    __syncthreads();
-    const float W = sW;
+    const int sub = loss_sub(), slot = loss_slot();
+    float wsum = 0.f;
+    if (sub == 0)
+        for (int n = slot; n < N; n += 256) wsum += class_w(class_weight, (int)target[n]);
+    const float W = slot_sum(sl, &sW, wsum);
     const float invW = 1.f / W;
     float local = 0.f;
     for (int n0 = 0; n0 < N; n0 += 256) {
@@ -201,21 +144,16 @@ __global__ __launch_bounds__(1024) void softmax_xent_focal_kernel(const float* l
         const bool ok = n < N;
         const float* l = logits + (size_t)(ok ? n : 0) * NC;
         const int tg = ok ? (int)target[n] : 0;
-        float mx = -INFINITY;
-        for (int j = sub; j < NC; j += 4) mx = fmaxf(mx, l[j]);
-        mx = fmaxf(mx, __shfl_xor(mx, 1));
-        mx = fmaxf(mx, __shfl_xor(mx, 2));
+        const float mx = row_max(l, NC, sub);
         float s = 0.f, so = 0.f;
         for (int j = sub; j < NC; j += 4) {
             const float e = expf(l[j] - mx);
             s += e;
             so += j == tg ? 0.f : e;
         }
-        s += __shfl_xor(s, 1);
-        s += __shfl_xor(s, 2);
-        so += __shfl_xor(so, 1);
-        so += __shfl_xor(so, 2);
-        const float wt = ok ? (class_weight ? class_weight[tg] : 1.f) : 0.f;
+        s = quad_sum(s);
+        so = quad_sum(so);
+        const float wt = ok ? class_w(class_weight, tg) : 0.f;
         const float li = mx + logf(s) - l[tg];
         const float u = so / s;
         const float pw = u > 0.f ? expf(gam * logf(u)) : (gam == 0.f ? 1.f : 0.f);
@@ -231,14 +169,8 @@ __global__ __launch_bounds__(1024) void softmax_xent_focal_kernel(const float* l
         }
     }
     __syncthreads();                       // (thread 0 has finished reading the W partials)
-    if (sub == 0) sl[slot] = local;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float s = 0.f;
-        for (int i = 0; i < 256; ++i) s += sl[i];
-        s = s * invW * weight;
-        loss_out[0] = loss_acc ? loss_out[0] + s : s;
-    }
+    const float total = slot_sum0(sl, local);
+    if (threadIdx.x == 0) loss_store(loss_out, loss_acc, total * invW * weight);
 }
 
 // Two-target loss of a mixed batch (TRAIN --mixup / --cutmix; ifcbk_batch_mix pairs image n with m = N - 1 - n): with a = target[n],
@@ -248,39 +180,27 @@ __global__ __launch_bounds__(1024) void softmax_xent_focal_kernel(const float* l
 //   d[n][j] = weight / W * [ (c1 h_n + eC SW) p[n][j] - c1 lam_n w[a] [j == a] - c1 (1 - lam_n) w[b] [j == b] - eC w[j] ]
 // Without weights W == N and this is timm's SoftTargetCrossEntropy on mixup_target; at lam == 1 it is softmax_xent_ls_kernel's function
 // (eps == 0: softmax_xent_w_kernel's), through this kernel's own operations.  a == b is legal: both one-hot terms land on one element.
-// softmax_xent_ls_kernel's shape: one 1024-thread block, 4 lanes per sample, fixed butterflies, one fixed-order slot pre-pass for W and
-// SW, fixed-order final sum -- bitwise reproducible; the smoothing term is summed from the same non-negative pieces.  Per sample, on top
-// of that kernel: 1 - lam_n, two products and an add for h_n (computed the same way in the pre-pass and in the row), a second -log p.
+// The pre-pass for W and SW and the smoothing term are softmax_xent_ls_kernel's.  Per sample, on top of that kernel: 1 - lam_n, two
+// products and an add for h_n (computed the same way in the pre-pass and in the row), a second -log p.
 // A target outside [0, NC) or a lam outside [0, 1] is the caller's fault; so is W == 0.
 __global__ __launch_bounds__(1024) void softmax_xent_mix_kernel(const float* logits, const int64_t* target, const float* lam,
                                                                 const float* class_weight, int N, int NC, float weight, float eps,
                                                                 float* loss_out, int loss_acc, float* dlogits) {
-    __shared__ float sl[256];
-    __shared__ float sk[256];
+    __shared__ float sl[2][LOSS_SLOTS];
     __shared__ float sW[2];
-    const int sub = threadIdx.x & 3, slot = threadIdx.x >> 2;
+    const int sub = loss_sub(), slot = loss_slot();
+    float wsum = 0.f, ksum = 0.f;
     if (sub == 0) {
-        float wsum = 0.f, ksum = 0.f;
         for (int n = slot; n < N; n += 256) {
             const float lm = lam[n];
-            const float ta = lm * (class_weight ? class_weight[(int)target[n]] : 1.f);
-            const float tb = (1.f - lm) * (class_weight ? class_weight[(int)target[N - 1 - n]] : 1.f);
+            const float ta = lm * class_w(class_weight, (int)target[n]);
+            const float tb = (1.f - lm) * class_w(class_weight, (int)target[N - 1 - n]);
             wsum += ta + tb;
         }
-        for (int k = slot; k < NC; k += 256) ksum += class_weight ? class_weight[k] : 1.f;
-        sl[slot] = wsum;
-        sk[slot] = ksum;
+        for (int k = slot; k < NC; k += 256) ksum += class_w(class_weight, k);
     }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float s = 0.f, k = 0.f;
-        for (int i = 0; i < 256; ++i) s += sl[i];
-        for (int i = 0; i < 256; ++i) k += sk[i];
-        sW[0] = s;
-        sW[1] = k;
-    }
-    __syncthreads();
-    const float W = sW[0], SW = sW[1];
+    const float2 sums = slot_sum2(sl, sW, wsum, ksum);
+    const float W = sums.x, SW = sums.y;
     const float invW = 1.f / W;
     const float g = weight / W;
     const float c1 = 1.f - eps, eC = eps / (float)NC;
@@ -289,23 +209,14 @@ __global__ __launch_bounds__(1024) void softmax_xent_mix_kernel(const float* log
         const int n = n0 + slot;
         const bool ok = n < N;
         const float* l = logits + (size_t)(ok ? n : 0) * NC;
-        float mx = -INFINITY;
-        for (int j = sub; j < NC; j += 4) mx = fmaxf(mx, l[j]);
-        mx = fmaxf(mx, __shfl_xor(mx, 1));
-        mx = fmaxf(mx, __shfl_xor(mx, 2));
-        float s = 0.f;
-        for (int j = sub; j < NC; j += 4) s += expf(l[j] - mx);
-        s += __shfl_xor(s, 1);
-        s += __shfl_xor(s, 2);
+        const float mx = row_max(l, NC, sub);
+        const float s = row_expsum(l, mx, NC, sub);
         const float ls = logf(s);
-        float q = 0.f;
-        for (int j = sub; j < NC; j += 4) q += (class_weight ? class_weight[j] : 1.f) * ((mx - l[j]) + ls);
-        q += __shfl_xor(q, 1);
-        q += __shfl_xor(q, 2);
+        const float q = smooth_q(l, class_weight, mx, ls, NC, sub);
         const int ta_i = ok ? (int)target[n] : 0, tb_i = ok ? (int)target[N - 1 - n] : 0;
         const float lm = ok ? lam[n] : 1.f;
-        const float ta = ok ? lm * (class_weight ? class_weight[ta_i] : 1.f) : 0.f;
-        const float tb = ok ? (1.f - lm) * (class_weight ? class_weight[tb_i] : 1.f) : 0.f;
+        const float ta = ok ? lm * class_w(class_weight, ta_i) : 0.f;
+        const float tb = ok ? (1.f - lm) * class_w(class_weight, tb_i) : 0.f;
         const float h = ta + tb;
         if (ok && sub == 0) {
             const float lia = mx + ls - l[ta_i], lib = mx + ls - l[tb_i];
@@ -317,18 +228,12 @@ __global__ __launch_bounds__(1024) void softmax_xent_mix_kernel(const float* log
             const float ha = c1 * ta, hb = c1 * tb;
             const float A = c1 * h + eC * SW;
             for (int j = sub; j < NC; j += 4)
-                d[j] = g * (A * (expf(l[j] - mx) * is) - (j == ta_i ? ha : 0.f) - (j == tb_i ? hb : 0.f) - eC * (class_weight ? class_weight[j] : 1.f));
+                d[j] = g * (A * (expf(l[j] - mx) * is) - (j == ta_i ? ha : 0.f) - (j == tb_i ? hb : 0.f) - eC * class_w(class_weight, j));
         }
     }
     __syncthreads();                       // (thread 0 has finished reading the pre-pass partials)
-    if (sub == 0) sl[slot] = local;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float s = 0.f;
-        for (int i = 0; i < 256; ++i) s += sl[i];
-        s = s * invW * weight;
-        loss_out[0] = loss_acc ? loss_out[0] + s : s;
-    }
+    const float total = slot_sum0(sl[0], local);
+    if (threadIdx.x == 0) loss_store(loss_out, loss_acc, total * invW * weight);
 }
 
 // Knowledge distillation (TRAIN --distill): Hinton's loss, the smoothed hard loss of softmax_xent_ls_kernel mixed with the KL divergence
@@ -337,9 +242,8 @@ __global__ __launch_bounds__(1024) void softmax_xent_mix_kernel(const float* log
 //   K       = 1 / N * sum_n sum_j q[n][j] (log q[n][j] - log r[n][j])                        (KL(q || r), "batchmean")
 //   loss    = a * ((1 - alpha) * H + alpha T^2 * K)
 //   d[n][j] = a * ((1 - alpha) * Dh[n][j] + alpha T / N * (r[n][j] - q[n][j]))
-// Class weights act on the hard term only.  softmax_xent_ls_kernel's shape: one 1024-thread block, 4 lanes per sample, fixed butterflies,
-// one fixed-order slot pre-pass for W and SW, fixed-order final sums (one chain of 256 slots for the hard terms, one for the soft ones)
-// -- bitwise reproducible.  Points of the arithmetic:
+// Class weights act on the hard term only.  softmax_xent_ls_kernel's pre-pass for W and SW; two final sums (one chain of 256 slots for the
+// hard terms, one for the soft ones).  Points of the arithmetic:
 //   x / T is a DIVISION of the rounded difference: arg_j = fl(fl(x_j - max) / T), correctly rounded, two roundings per argument (a product
 //     with a rounded 1 / T would be three).  T > 0, so the row's maximum is the maximum of x / T as well and its argument is exactly 0:
 //     both softened sums are >= 1, as s is.
@@ -358,27 +262,16 @@ __global__ __launch_bounds__(1024) void softmax_xent_mix_kernel(const float* log
 __global__ __launch_bounds__(1024) void softmax_xent_distill_kernel(const float* logits, const int64_t* target, const float* teacher,
                                                                     const float* class_weight, int N, int NC, float weight, float eps,
                                                                     float alpha, float T, float* loss_out, int loss_acc, float* dlogits) {
-    __shared__ float sl[256];
-    __shared__ float sk[256];
+    __shared__ float sl[2][LOSS_SLOTS];
     __shared__ float sW[2];
-    const int sub = threadIdx.x & 3, slot = threadIdx.x >> 2;
+    const int sub = loss_sub(), slot = loss_slot();
+    float wsum = 0.f, ksum = 0.f;
     if (sub == 0) {
-        float wsum = 0.f, ksum = 0.f;
-        for (int n = slot; n < N; n += 256) wsum += class_weight ? class_weight[(int)target[n]] : 1.f;
-        for (int k = slot; k < NC; k += 256) ksum += class_weight ? class_weight[k] : 1.f;
-        sl[slot] = wsum;
-        sk[slot] = ksum;
+        for (int n = slot; n < N; n += 256) wsum += class_w(class_weight, (int)target[n]);
+        for (int k = slot; k < NC; k += 256) ksum += class_w(class_weight, k);
     }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float s = 0.f, k = 0.f;
-        for (int i = 0; i < 256; ++i) s += sl[i];
-        for (int i = 0; i < 256; ++i) k += sk[i];
-        sW[0] = s;
-        sW[1] = k;
-    }
-    __syncthreads();
-    const float W = sW[0], SW = sW[1];
+    const float2 sums = slot_sum2(sl, sW, wsum, ksum);
+    const float W = sums.x, SW = sums.y;
     const float invW = 1.f / W;
     const float c1 = 1.f - eps, eC = eps / (float)NC;
     const float ch = 1.f - alpha;                     // weight of the hard term
@@ -396,10 +289,8 @@ __global__ __launch_bounds__(1024) void softmax_xent_distill_kernel(const float*
             mx = fmaxf(mx, l[j]);
             mz = fmaxf(mz, z[j]);
         }
-        mx = fmaxf(mx, __shfl_xor(mx, 1));
-        mx = fmaxf(mx, __shfl_xor(mx, 2));
-        mz = fmaxf(mz, __shfl_xor(mz, 1));
-        mz = fmaxf(mz, __shfl_xor(mz, 2));
+        mx = quad_max(mx);
+        mz = quad_max(mz);
         float s = 0.f, sr = 0.f, sq = 0.f;
         for (int j = sub; j < NC; j += 4) {
             const float dl = l[j] - mx, dz = z[j] - mz;
@@ -407,29 +298,24 @@ __global__ __launch_bounds__(1024) void softmax_xent_distill_kernel(const float*
             sr += expf(dl / T);
             sq += expf(dz / T);
         }
-        s += __shfl_xor(s, 1);
-        s += __shfl_xor(s, 2);
-        sr += __shfl_xor(sr, 1);
-        sr += __shfl_xor(sr, 2);
-        sq += __shfl_xor(sq, 1);
-        sq += __shfl_xor(sq, 2);
+        s = quad_sum(s);
+        sr = quad_sum(sr);
+        sq = quad_sum(sq);
         const float ls = logf(s), lsr = logf(sr), lsq = logf(sq);
         const float isr = 1.f / sr, isq = 1.f / sq;
         float q = 0.f, kl = 0.f;
         for (int j = sub; j < NC; j += 4) {
-            q += (class_weight ? class_weight[j] : 1.f) * ((mx - l[j]) + ls);
+            smooth_q_add(q, class_w(class_weight, j), mx, l[j], ls);
             const float ar = (l[j] - mx) / T, aq = (z[j] - mz) / T;
             const float qj = expf(aq) * isq;
             const float diff = (aq - lsq) - (ar - lsr);
             const float term = qj * diff;
             kl += qj > 0.f ? term : 0.f;
         }
-        q += __shfl_xor(q, 1);
-        q += __shfl_xor(q, 2);
-        kl += __shfl_xor(kl, 1);
-        kl += __shfl_xor(kl, 2);
+        q = quad_sum(q);
+        kl = quad_sum(kl);
         const int tg = ok ? (int)target[n] : 0;
-        const float wt = ok ? (class_weight ? class_weight[tg] : 1.f) : 0.f;
+        const float wt = ok ? class_w(class_weight, tg) : 0.f;
         const float hard = c1 * wt;
         if (ok && sub == 0) {
             const float li = mx + ls - l[tg];
@@ -441,7 +327,7 @@ __global__ __launch_bounds__(1024) void softmax_xent_distill_kernel(const float*
             const float is = 1.f / s;
             const float A = hard + eC * SW;
             for (int j = sub; j < NC; j += 4) {
-                const float dh = g * (A * (expf(l[j] - mx) * is) - (j == tg ? hard : 0.f) - eC * (class_weight ? class_weight[j] : 1.f));
+                const float dh = smooth_dlogit(g, A, expf(l[j] - mx) * is, j == tg ? hard : 0.f, eC, class_w(class_weight, j));
                 const float rj = expf((l[j] - mx) / T) * isr, qj = expf((z[j] - mz) / T) * isq;
                 const float soft = cd * (rj - qj);
                 d[j] = ch * dh + soft;
@@ -449,20 +335,12 @@ __global__ __launch_bounds__(1024) void softmax_xent_distill_kernel(const float*
         }
     }
     __syncthreads();                       // (thread 0 has finished reading the pre-pass partials)
-    if (sub == 0) {
-        sl[slot] = local;
-        sk[slot] = localk;
-    }
-    __syncthreads();
+    slot_put2(sl, local, localk);
     if (threadIdx.x == 0) {
-        float s = 0.f, k = 0.f;
-        for (int i = 0; i < 256; ++i) s += sl[i];
-        for (int i = 0; i < 256; ++i) k += sk[i];
-        const float H = s * invW;
-        const float K = k * (1.f / (float)N);
+        const float H = slot_total(sl[0]) * invW;
+        const float K = slot_total(sl[1]) * (1.f / (float)N);
         const float soft = cs * K;
-        const float v = weight * (ch * H + soft);
-        loss_out[0] = loss_acc ? loss_out[0] + v : v;
+        loss_store(loss_out, loss_acc, weight * (ch * H + soft));
     }
 }
 
@@ -500,11 +378,19 @@ extern "C" int ifcbk_softmax_acc(ifcbk_ctx* ctx, const float* logits, int N, int
     return IFCBK_OK;
 }
 
+// The refusals the five entry points below share.  name: the entry point's, without its ifcbk_ prefix; operands: logits, target and
+// loss_out are all there; label_smoothing: 0 from the entry points that have none.
+static int loss_refused(ifcbk_ctx* ctx, const char* name, int N, int NC, float label_smoothing, bool operands) {
+    if (N <= 0 || NC <= 0) IFCBK_FAIL(ctx, IFCBK_EINVAL, "%s: empty", name);
+    if (!(label_smoothing >= 0.f && label_smoothing <= 1.f)) IFCBK_FAIL(ctx, IFCBK_EINVAL, "%s: label_smoothing outside [0, 1]", name);
+    if (!operands) IFCBK_FAIL(ctx, IFCBK_EINVAL, "%s: NULL operand", name);
+    return IFCBK_OK;
+}
+
 extern "C" int ifcbk_softmax_xent_w(ifcbk_ctx* ctx, const float* logits, const int64_t* target, const float* class_weight, int N, int NC,
                                     float weight, float* loss_out, int loss_accumulate, float* dlogits, void* stream) {
-    if (N <= 0 || NC <= 0) IFCBK_FAIL(ctx, IFCBK_EINVAL, "softmax_xent_w: empty");
+    if (int e = loss_refused(ctx, "softmax_xent_w", N, NC, 0.f, logits && target && loss_out)) return e;
     if (!class_weight) IFCBK_FAIL(ctx, IFCBK_EINVAL, "softmax_xent_w: class_weight is NULL (the unweighted loss is ifcbk_softmax_xent)");
-    if (!logits || !target || !loss_out) IFCBK_FAIL(ctx, IFCBK_EINVAL, "softmax_xent_w: NULL operand");
     hipLaunchKernelGGL(softmax_xent_w_kernel, dim3(1), dim3(1024), 0, ST, logits, target, class_weight, N, NC, weight, loss_out,
                        loss_accumulate, dlogits);
     IFCBK_LAUNCH_CHECK(ctx, "softmax_xent_w");
@@ -514,9 +400,7 @@ extern "C" int ifcbk_softmax_xent_w(ifcbk_ctx* ctx, const float* logits, const i
 extern "C" int ifcbk_softmax_xent_ls(ifcbk_ctx* ctx, const float* logits, const int64_t* target, const float* class_weight, int N, int NC,
                                      float weight, float label_smoothing, float* loss_out, int loss_accumulate, float* dlogits,
                                      void* stream) {
-    if (N <= 0 || NC <= 0) IFCBK_FAIL(ctx, IFCBK_EINVAL, "softmax_xent_ls: empty");
-    if (!(label_smoothing >= 0.f && label_smoothing <= 1.f)) IFCBK_FAIL(ctx, IFCBK_EINVAL, "softmax_xent_ls: label_smoothing outside [0, 1]");
-    if (!logits || !target || !loss_out) IFCBK_FAIL(ctx, IFCBK_EINVAL, "softmax_xent_ls: NULL operand");
+    if (int e = loss_refused(ctx, "softmax_xent_ls", N, NC, label_smoothing, logits && target && loss_out)) return e;
     hipLaunchKernelGGL(softmax_xent_ls_kernel, dim3(1), dim3(1024), 0, ST, logits, target, class_weight, N, NC, weight, label_smoothing,
                        loss_out, loss_accumulate, dlogits);
     IFCBK_LAUNCH_CHECK(ctx, "softmax_xent_ls");
@@ -525,9 +409,8 @@ extern "C" int ifcbk_softmax_xent_ls(ifcbk_ctx* ctx, const float* logits, const 
 
 extern "C" int ifcbk_softmax_xent_focal(ifcbk_ctx* ctx, const float* logits, const int64_t* target, const float* class_weight, int N, int NC,
                                         float weight, float gamma, float* loss_out, int loss_accumulate, float* dlogits, void* stream) {
-    if (N <= 0 || NC <= 0) IFCBK_FAIL(ctx, IFCBK_EINVAL, "softmax_xent_focal: empty");
+    if (int e = loss_refused(ctx, "softmax_xent_focal", N, NC, 0.f, logits && target && loss_out)) return e;
     if (!(gamma >= 0.f && gamma <= FLT_MAX)) IFCBK_FAIL(ctx, IFCBK_EINVAL, "softmax_xent_focal: gamma negative or not finite");
-    if (!logits || !target || !loss_out) IFCBK_FAIL(ctx, IFCBK_EINVAL, "softmax_xent_focal: NULL operand");
     hipLaunchKernelGGL(softmax_xent_focal_kernel, dim3(1), dim3(1024), 0, ST, logits, target, class_weight, N, NC, weight, gamma, loss_out,
                        loss_accumulate, dlogits);
     IFCBK_LAUNCH_CHECK(ctx, "softmax_xent_focal");
@@ -537,10 +420,8 @@ extern "C" int ifcbk_softmax_xent_focal(ifcbk_ctx* ctx, const float* logits, con
 extern "C" int ifcbk_softmax_xent_mix(ifcbk_ctx* ctx, const float* logits, const int64_t* target, const float* lam, const float* class_weight,
                                       int N, int NC, float weight, float label_smoothing, float* loss_out, int loss_accumulate,
                                       float* dlogits, void* stream) {
-    if (N <= 0 || NC <= 0) IFCBK_FAIL(ctx, IFCBK_EINVAL, "softmax_xent_mix: empty");
+    if (int e = loss_refused(ctx, "softmax_xent_mix", N, NC, label_smoothing, logits && target && loss_out)) return e;
     if (!lam) IFCBK_FAIL(ctx, IFCBK_EINVAL, "softmax_xent_mix: lam is NULL (the one-target losses are ifcbk_softmax_xent_w / _ls)");
-    if (!(label_smoothing >= 0.f && label_smoothing <= 1.f)) IFCBK_FAIL(ctx, IFCBK_EINVAL, "softmax_xent_mix: label_smoothing outside [0, 1]");
-    if (!logits || !target || !loss_out) IFCBK_FAIL(ctx, IFCBK_EINVAL, "softmax_xent_mix: NULL operand");
     hipLaunchKernelGGL(softmax_xent_mix_kernel, dim3(1), dim3(1024), 0, ST, logits, target, lam, class_weight, N, NC, weight, label_smoothing,
                        loss_out, loss_accumulate, dlogits);
     IFCBK_LAUNCH_CHECK(ctx, "softmax_xent_mix");
@@ -550,12 +431,10 @@ extern "C" int ifcbk_softmax_xent_mix(ifcbk_ctx* ctx, const float* logits, const
 extern "C" int ifcbk_softmax_xent_distill(ifcbk_ctx* ctx, const float* logits, const int64_t* target, const float* teacher,
                                           const float* class_weight, int N, int NC, float weight, float label_smoothing, float alpha,
                                           float temperature, float* loss_out, int loss_accumulate, float* dlogits, void* stream) {
-    if (N <= 0 || NC <= 0) IFCBK_FAIL(ctx, IFCBK_EINVAL, "softmax_xent_distill: empty");
+    if (int e = loss_refused(ctx, "softmax_xent_distill", N, NC, label_smoothing, logits && target && loss_out)) return e;
     if (!teacher) IFCBK_FAIL(ctx, IFCBK_EINVAL, "softmax_xent_distill: teacher is NULL (the losses without a teacher are ifcbk_softmax_xent_w / _ls)");
-    if (!(label_smoothing >= 0.f && label_smoothing <= 1.f)) IFCBK_FAIL(ctx, IFCBK_EINVAL, "softmax_xent_distill: label_smoothing outside [0, 1]");
     if (!(alpha >= 0.f && alpha <= 1.f)) IFCBK_FAIL(ctx, IFCBK_EINVAL, "softmax_xent_distill: alpha outside [0, 1]");
     if (!(temperature > 0.f && temperature <= FLT_MAX)) IFCBK_FAIL(ctx, IFCBK_EINVAL, "softmax_xent_distill: temperature is not a finite positive number");
-    if (!logits || !target || !loss_out) IFCBK_FAIL(ctx, IFCBK_EINVAL, "softmax_xent_distill: NULL operand");
     hipLaunchKernelGGL(softmax_xent_distill_kernel, dim3(1), dim3(1024), 0, ST, logits, target, teacher, class_weight, N, NC, weight,
                        label_smoothing, alpha, temperature, loss_out, loss_accumulate, dlogits);
     IFCBK_LAUNCH_CHECK(ctx, "softmax_xent_distill");

@@ -1,6 +1,7 @@
 // Pooling, GAP->dropout->FC head, softmax / cross-entropy, Adam/SGD, layout conversion.  HBM-bound kernels:
 // NHWC bf16, one 16-byte chunk (8 channels) per lane, consecutive lanes on consecutive chunks.
 #include "common.h"
+#include "loss_rows.h"
 #include <math.h>
 #include <stdlib.h>
 
@@ -558,26 +559,20 @@ __global__ void dropout_mask_kernel(uint8_t* mask, int64_t n, float p, uint64_t 
 }
 
 // ---------------------------------------------------------------- loss (single block: deterministic mean)
-// 4 lanes per sample (classes j = sub, sub+4, ...: adjacent lanes read adjacent logits), fixed butterfly for max and
-// sum, per-sample losses summed in a fixed order by thread 0 -> bitwise reproducible.
+// The shape and the pieces of loss_rows.h (4 lanes per sample, fixed butterflies, per-sample losses summed in a fixed order by
+// thread 0 -> bitwise reproducible), which the weighted, smoothed, focal, mixed and distilled kernels of loss.hip share.
 __global__ __launch_bounds__(1024) void softmax_xent_kernel(const float* logits, const int64_t* target, int N, int NC,
                                                             float weight, float* loss_out, int loss_acc, float* dlogits) {
-    __shared__ float sl[256];
-    const int sub = threadIdx.x & 3, slot = threadIdx.x >> 2;
+    __shared__ float sl[LOSS_SLOTS];
+    const int sub = loss_sub(), slot = loss_slot();
     const float invN = 1.f / (float)N;
     float local = 0.f;
     for (int n0 = 0; n0 < N; n0 += 256) {
         const int n = n0 + slot;
         const bool ok = n < N;
         const float* l = logits + (size_t)(ok ? n : 0) * NC;
-        float mx = -INFINITY;
-        for (int j = sub; j < NC; j += 4) mx = fmaxf(mx, l[j]);
-        mx = fmaxf(mx, __shfl_xor(mx, 1));
-        mx = fmaxf(mx, __shfl_xor(mx, 2));
-        float s = 0.f;
-        for (int j = sub; j < NC; j += 4) s += expf(l[j] - mx);
-        s += __shfl_xor(s, 1);
-        s += __shfl_xor(s, 2);
+        const float mx = row_max(l, NC, sub);
+        const float s = row_expsum(l, mx, NC, sub);
         const int tg = ok ? (int)target[n] : 0;
         if (ok && sub == 0) local += mx + logf(s) - l[tg];
         if (ok && dlogits) {
@@ -586,14 +581,8 @@ __global__ __launch_bounds__(1024) void softmax_xent_kernel(const float* logits,
             for (int j = sub; j < NC; j += 4) d[j] = weight * invN * (expf(l[j] - mx) * is - (j == tg ? 1.f : 0.f));
         }
     }
-    if (sub == 0) sl[slot] = local;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float s = 0.f;
-        for (int i = 0; i < 256; ++i) s += sl[i];
-        s = s * invN * weight;
-        loss_out[0] = loss_acc ? loss_out[0] + s : s;
-    }
+    const float total = slot_sum0(sl, local);
+    if (threadIdx.x == 0) loss_store(loss_out, loss_acc, total * invN * weight);
 }
 __global__ void softmax_kernel(const float* logits, int N, int NC, float* probs) {
     int n = blockIdx.x * blockDim.x + threadIdx.x;

@@ -102,6 +102,29 @@ def test_every_entry_point_is_called_by_a_test():
     assert not [n for n in EXEMPT_API if n not in api], 'an exemption names an entry point that is gone'
 
 
+def test_the_loss_row_reduction_is_written_once():
+    """the quad butterflies and the fixed-order slot sums of the six fused loss kernels stand once, in loss_rows.h: a loss variant that
+    pastes a further copy instead of calling the shared pieces fails here"""
+    shared = open(os.path.join(CSRC, 'loss_rows.h')).read()
+    loss = open(os.path.join(CSRC, 'loss.hip')).read()
+    head = open(os.path.join(CSRC, 'pool_head.hip')).read()
+    assert len(_kernels('loss.hip')) == 6 and sum(k.startswith('softmax_xent_') for k in _kernels('loss.hip')) == 5
+    m = re.search(r'void\s+softmax_xent_kernel\s*\(.*?\n}\n', head, re.S)
+    assert m and 'for (int n0 = 0; n0 < N; n0 += 256)' in m.group(0) and 'loss_store(' in m.group(0)
+    slot_loop = r'for\s*\(\s*int\s+i\s*=\s*0\s*;\s*i\s*<\s*\w+\s*;\s*\+\+i\s*\)'
+    for where, text in (('loss.hip', loss), ('softmax_xent_kernel', m.group(0))):
+        assert '__shfl_xor' not in text, where
+        assert 'for (int i = 0; i < 256; ++i)' not in text and not re.search(slot_loop, text), where
+        assert '#include "loss_rows.h"' in (loss if where == 'loss.hip' else head), where
+    # each butterfly (two exchange steps), the slot sum and each of its callers is defined once, and the butterflies only there
+    assert len(re.findall(r'__shfl_xor', shared)) == 4 and len(re.findall(slot_loop, shared)) == 1
+    assert 'for (int i = 0; i < LOSS_SLOTS; ++i) s += sl[i];' in shared and re.search(r'constexpr int LOSS_SLOTS = 256;', shared)
+    for fn in ('quad_max', 'quad_sum', 'row_max', 'row_expsum', 'class_w', 'slot_total', 'slot_sum0', 'slot_sum', 'slot_sum2', 'loss_store'):
+        assert len(re.findall(r'__device__ __forceinline__ \w+ %s\(' % fn, shared)) == 1, fn
+    rule = re.search(r'^%\.o:(.*)$', open(os.path.join(CSRC, 'Makefile')).read(), re.M).group(1)
+    assert 'loss_rows.h' in rule.split()
+
+
 def test_the_library_is_built_without_flags_that_change_rounding():
     """op_bounds.py counts sqrtf and / as one rounding each and a * b + c as one or two: true under -ffp-contract=on without
     fast-math, reciprocal or denormal flags"""
