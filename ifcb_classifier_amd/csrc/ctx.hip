@@ -134,10 +134,21 @@ extern "C" const char* ifcbk_last_error(ifcbk_ctx* c) { return c ? c->err : g_cr
 // the weight average's slice of an optimizer op (TRAIN --ema): the operand behind those of the plain step, p[4] of IFCBK_OP_ADAM (its
 // weight: f[6]) and p[3] of IFCBK_OP_SGD (f[4]); NULL, what a zeroed op holds, is the step without an average
 static float* op_ema(const ifcbk_op* o) { return (float*)o->p[o->kind == IFCBK_OP_ADAM ? 4 : 3]; }
+// the clip state of an optimizer op (TRAIN --clip-grad), the operand behind the average: p[5] of IFCBK_OP_ADAM (max_norm: f[7]) and p[4]
+// of IFCBK_OP_SGD (f[5]); NULL, what a zeroed op holds, is the step without clipping
+static float* op_clip(const ifcbk_op* o) { return (float*)o->p[o->kind == IFCBK_OP_ADAM ? 5 : 4]; }
 
 static int run_one(ifcbk_ctx* c, const ifcbk_op* o, void* st) {
     void* const* p = o->p;
     const int acc = o->flags & 1, pacc = (o->flags >> 1) & 1;
+    // a clip state (TRAIN --clip-grad) rides on the two optimizer kinds: NULL, what a zeroed op holds, takes the cases below untouched;
+    // a state sends the op to the clipping entry points with the same operands and max_norm from f[7] / f[5]
+    if (o->kind == IFCBK_OP_ADAM && op_clip(o))
+        return ifcbk_adam_clip_flat(c, (float*)p[0], (const float*)p[1], (float*)p[2], (float*)p[3], op_ema(o), o->i[0], o->f[0], o->f[1],
+                                    o->f[2], o->f[3], o->f[4], (int)o->i[1], o->f[5], o->f[6], o->f[7], op_clip(o), st);
+    if (o->kind == IFCBK_OP_SGD && op_clip(o))
+        return ifcbk_sgd_clip_flat(c, (float*)p[0], (const float*)p[1], (float*)p[2], op_ema(o), o->i[0], o->f[0], o->f[1], o->f[2],
+                                   o->f[3], o->f[4], o->f[5], op_clip(o), st);
     // label smoothing (TRAIN --label-smoothing) rides on the two loss kinds: f[1] != 0 is the smoothing factor and goes to the smoothed
     // kernel, with p[4] as the class weights of the _W kind and none for the plain kind; f[1] == 0 takes the cases below untouched
     if ((o->kind == IFCBK_OP_SOFTMAX_XENT || o->kind == IFCBK_OP_SOFTMAX_XENT_W) && o->f[1] != 0.f && o->f[2] != 0.f)
@@ -744,8 +755,9 @@ extern "C" int ifcbk_op_cost(const ifcbk_op* o, double* flops, double* bytes) {
             by = (double)d.N * d.HW * d.C * 2;
             break;
         }
-        case IFCBK_OP_ADAM: by = (double)o->i[0] * (28 + (o->p[4] ? 8 : 0)); break;      // (+ the weight average: read and written)
-        case IFCBK_OP_SGD: by = (double)o->i[0] * ((o->p[2] ? 20 : 12) + (o->p[3] ? 8 : 0)); break;
+        // (+ the weight average: read and written; + the norm's pass over the gradient when the op clips)
+        case IFCBK_OP_ADAM: by = (double)o->i[0] * (28 + (o->p[4] ? 8 : 0) + (o->p[5] ? 4 : 0)); break;
+        case IFCBK_OP_SGD: by = (double)o->i[0] * ((o->p[2] ? 20 : 12) + (o->p[3] ? 8 : 0) + (o->p[4] ? 4 : 0)); break;
         case IFCBK_OP_SOFTMAX_XENT: case IFCBK_OP_SOFTMAX_XENT_W:
             if (o->p[6]) {                  // the distillation loss: logits and teacher in, dlogits out (when asked for), targets
                 fl = (double)o->i[0] * o->i[1] * 30;

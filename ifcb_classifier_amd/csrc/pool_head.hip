@@ -596,8 +596,11 @@ __global__ void softmax_kernel(const float* logits, int N, int NC, float* probs)
 // ---------------------------------------------------------------- optimizers (flat)
 __global__ __launch_bounds__(256) void adam_kernel(float* p, const float* g, float* m, float* v, int64_t n, float lr,
                                                    float b1, float b2, float eps, float wd, float bc1, float sbc2,
-                                                   float gscale, float* ema, float ew) {
+                                                   float gscale, float* ema, float ew, const float* clip) {
     // ema (nullable, wave-uniform): the weight average e += ew * (p - e) of the p this step writes, taken from the registers
+    // clip (nullable, wave-uniform): the state ifcbk_grad_norm left (grad_clip.hip); the gradient scale is then gscale * clip[1], formed
+    // once and used where gscale is: coef == 1 leaves the step's bits alone, gscale == 1 makes the scale coef itself
+    if (clip) gscale *= clip[1];
     int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
     if (i >= n) return;
     if (i + 4 <= n) {
@@ -635,9 +638,10 @@ __global__ __launch_bounds__(256) void adam_kernel(float* p, const float* g, flo
     }
 }
 __global__ __launch_bounds__(256) void sgd_kernel(float* p, const float* g, float* mom, int64_t n, float lr, float mu,
-                                                  float wd, float gscale, float* ema, float ew) {
+                                                  float wd, float gscale, float* ema, float ew, const float* clip) {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    if (clip) gscale *= clip[1];                              // (as adam_kernel: the clip coefficient of ifcbk_grad_norm)
     float gr = g[i] * gscale + wd * p[i];
     if (mom) {
         float b = mu * mom[i] + gr;
@@ -840,34 +844,53 @@ extern "C" int ifcbk_softmax(ifcbk_ctx* ctx, const float* logits, int N, int NC,
 
 // the weight of a fused weight average: [0, 1] (a NaN fails both comparisons); 0 is "no update", which the callers launch as ema = NULL
 static bool ema_w_ok(float w) { return w >= 0.f && w <= 1.f; }
-extern "C" int ifcbk_adam_ema_flat(ifcbk_ctx* ctx, float* p, const float* g, float* m, float* v, float* ema, int64_t n, float lr,
-                                   float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale, float ema_w,
-                                   void* stream) {
+// the optimizer steps with every nullable operand: the weight average (TRAIN --ema) and the clip state (TRAIN --clip-grad).  With a clip
+// state the norm of grad_scale * g is taken first (ifcbk_grad_norm: two launches), then the update reads its coefficient from the state
+extern "C" int ifcbk_adam_clip_flat(ifcbk_ctx* ctx, float* p, const float* g, float* m, float* v, float* ema, int64_t n, float lr,
+                                    float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale, float ema_w,
+                                    float max_norm, float* clip_state, void* stream) {
     if (step < 1) IFCBK_FAIL(ctx, IFCBK_EINVAL, "adam: step must be >= 1");
     if (ema && !ema_w_ok(ema_w)) IFCBK_FAIL(ctx, IFCBK_EINVAL, "adam: ema_w %g outside [0, 1]", (double)ema_w);
     if (ema && ((uintptr_t)ema & 15) != ((uintptr_t)p & 15)) IFCBK_FAIL(ctx, IFCBK_EINVAL, "adam: ema must be aligned as p is");
     if (ema_w == 0.f) ema = nullptr;
+    if (clip_state) {
+        const int rc = ifcbk_grad_norm(ctx, g, n, grad_scale, max_norm, clip_state, stream);
+        if (rc) return rc;
+    }
     float bc1 = 1.f - powf(beta1, (float)step);
     float sbc2 = sqrtf(1.f - powf(beta2, (float)step));
-    hipLaunchKernelGGL(adam_kernel, dim3(cdiv(cdiv(n, 4), 256)), dim3(256), 0, ST, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, sbc2, grad_scale, ema, ema_w);
+    hipLaunchKernelGGL(adam_kernel, dim3(cdiv(cdiv(n, 4), 256)), dim3(256), 0, ST, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, sbc2, grad_scale, ema, ema_w, (const float*)clip_state);
     IFCBK_LAUNCH_CHECK(ctx, "adam");
     return 0;
 }
+extern "C" int ifcbk_adam_ema_flat(ifcbk_ctx* ctx, float* p, const float* g, float* m, float* v, float* ema, int64_t n, float lr,
+                                   float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale, float ema_w,
+                                   void* stream) {
+    return ifcbk_adam_clip_flat(ctx, p, g, m, v, ema, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, ema_w, 0.f, nullptr, stream);
+}
 extern "C" int ifcbk_adam_flat(ifcbk_ctx* ctx, float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1,
                                float beta2, float eps, float weight_decay, int step, float grad_scale, void* stream) {
-    return ifcbk_adam_ema_flat(ctx, p, g, m, v, nullptr, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, 0.f, stream);
+    return ifcbk_adam_clip_flat(ctx, p, g, m, v, nullptr, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, 0.f, 0.f, nullptr, stream);
 }
-extern "C" int ifcbk_sgd_ema_flat(ifcbk_ctx* ctx, float* p, const float* g, float* mom, float* ema, int64_t n, float lr, float momentum,
-                                  float weight_decay, float grad_scale, float ema_w, void* stream) {
+extern "C" int ifcbk_sgd_clip_flat(ifcbk_ctx* ctx, float* p, const float* g, float* mom, float* ema, int64_t n, float lr, float momentum,
+                                   float weight_decay, float grad_scale, float ema_w, float max_norm, float* clip_state, void* stream) {
     if (ema && !ema_w_ok(ema_w)) IFCBK_FAIL(ctx, IFCBK_EINVAL, "sgd: ema_w %g outside [0, 1]", (double)ema_w);
     if (ema_w == 0.f) ema = nullptr;
-    hipLaunchKernelGGL(sgd_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ST, p, g, mom, n, lr, momentum, weight_decay, grad_scale, ema, ema_w);
+    if (clip_state) {
+        const int rc = ifcbk_grad_norm(ctx, g, n, grad_scale, max_norm, clip_state, stream);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(sgd_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ST, p, g, mom, n, lr, momentum, weight_decay, grad_scale, ema, ema_w, (const float*)clip_state);
     IFCBK_LAUNCH_CHECK(ctx, "sgd");
     return 0;
 }
+extern "C" int ifcbk_sgd_ema_flat(ifcbk_ctx* ctx, float* p, const float* g, float* mom, float* ema, int64_t n, float lr, float momentum,
+                                  float weight_decay, float grad_scale, float ema_w, void* stream) {
+    return ifcbk_sgd_clip_flat(ctx, p, g, mom, ema, n, lr, momentum, weight_decay, grad_scale, ema_w, 0.f, nullptr, stream);
+}
 extern "C" int ifcbk_sgd_flat(ifcbk_ctx* ctx, float* p, const float* g, float* mom, int64_t n, float lr, float momentum,
                               float weight_decay, float grad_scale, void* stream) {
-    return ifcbk_sgd_ema_flat(ctx, p, g, mom, nullptr, n, lr, momentum, weight_decay, grad_scale, 0.f, stream);
+    return ifcbk_sgd_clip_flat(ctx, p, g, mom, nullptr, n, lr, momentum, weight_decay, grad_scale, 0.f, 0.f, nullptr, stream);
 }
 
 extern "C" int ifcbk_nchw_to_nhwc(ifcbk_ctx* ctx, const float* x, int N, int C, int H, int W, int Cpad, int dtype,

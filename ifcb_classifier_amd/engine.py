@@ -87,7 +87,7 @@ class Engine:
 
     def __init__(self, net, device=0, max_batch=32, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, dtype='bf16', optimizer='adam',
                  momentum=0.0, plan_only=False, train_batch=None, dp_world=None, class_weights=None, weight_decay=0.0,
-                 label_smoothing=0.0, focal_gamma=0.0, mix=False, ema_decay=None, ema_warmup=True, distill=None):
+                 label_smoothing=0.0, focal_gamma=0.0, mix=False, ema_decay=None, ema_warmup=True, distill=None, clip_grad=None):
         # dp_world: world size of the data-parallel job this replica belongs to (None: WORLD_SIZE of the launcher, else an
         # initialised torch.distributed group, else 1) -- it picks the program-lane default, and train_step_ddp checks it
         self._dp_world_arg = None if dp_world is None else int(dp_world)
@@ -142,6 +142,15 @@ class Engine:
         self.ema_updates = 0              # t of the decay schedule: updates since E was last initialised
         self._ema_w = 0.0
         self._ema_view = None             # (P, RB, stale flag) saved by ema_weights() while the averaged model stands in P / RB
+        # additive (TRAIN --clip-grad): torch.nn.utils.clip_grad_norm_(parameters, clip_grad) ahead of every optimizer step, on the device:
+        # the step's one optimizer op takes the norm of the whole of G (ifcbk_grad_norm) into ``clip_state`` and its update reads the
+        # coefficient from there (its p[5] / p[4]); nothing is waited for.  None: no state, and plans, op tables and launches are what
+        # they were
+        self.clip_grad = None if clip_grad is None else float(clip_grad)
+        if self.clip_grad is not None and not 0.0 < self.clip_grad < math.inf:      # (a NaN fails both comparisons)
+            raise ValueError('clip_grad must be a finite number > 0, or None for no gradient clipping')
+        if self.clip_grad is not None and not 0.0 < C.c_float(self.clip_grad).value < math.inf:
+            raise ValueError('clip_grad %r is not a finite fp32 number > 0' % self.clip_grad)
         self.net = net
         if dtype not in ('bf16', 'fp32'):
             raise ValueError("dtype must be 'bf16' (performance) or 'fp32' (parity mode)")
@@ -215,6 +224,11 @@ class Engine:
         self.M = torch.zeros(off, dtype=torch.float32, device=dev)
         self.V = torch.zeros(off, dtype=torch.float32, device=dev)
         self.E = torch.zeros(off, dtype=torch.float32, device=dev) if self.ema_decay is not None else None      # layout of P
+        # the clip state: norm, coefficient, the epoch's two running figures, and the norm kernel's per-block partial sums
+        self.clip_state = None
+        if self.clip_grad is not None:
+            self.clip_state = torch.zeros(int(self.ctx.lib.ifcbk_grad_clip_state_floats()), dtype=torch.float32, device=dev)
+            assert self.clip_state.data_ptr() % 16 == 0
         self.pviews, self.gviews = {}, {}
         for key, (o, n, shape, kind, node) in self.poff.items():
             if kind == 'conv':
@@ -409,6 +423,21 @@ class Engine:
         self.packed = False
         self.eval_stats_ready = False
         self.ema_stale = True             # (the optimizer paths do not come through here: only writes from outside restart the average)
+
+    # ------------------------------------------------------------------ gradient clipping (TRAIN --clip-grad)
+    def grad_clip_stats(self):
+        """-> (norm of the last step's gradient before clipping, its coefficient, the largest norm and the number of clipped steps since
+        reset_grad_clip_stats).  One 16-byte device-to-host read on the engine's stream: it waits for the steps queued there"""
+        if self.clip_state is None:
+            raise RuntimeError('grad_clip_stats: this engine was built without clip_grad')
+        norm, coef, top, clipped = self.clip_state[:4].tolist()
+        return norm, coef, top, int(clipped)
+
+    def reset_grad_clip_stats(self):
+        """zero the two running figures (largest norm, clipped steps): the start of an epoch's report"""
+        if self.clip_state is None:
+            raise RuntimeError('reset_grad_clip_stats: this engine was built without clip_grad')
+        self.clip_state[2:4].zero_()
 
     # ------------------------------------------------------------------ weight average (TRAIN --ema)
     def _ema_begin_step(self, update=True):
@@ -894,6 +923,8 @@ class Engine:
         from .dp import run_overlapped
         run_overlapped(self.ddp_segments(pl), lambda seg: self.run(seg[0]), self.G, all_reduce, mark)
         self.step_count += 1
+        # with clipping the op takes its norm over the REDUCED buffer with this grad_scale, i.e. the norm of the averaged gradient: every
+        # rank holds the same bits of G behind the all-reduce, so every rank computes the same coefficient and no collective is needed
         self._set_update(pl.adam_pack.arr[0], 1.0 / world)
         self.run(pl.adam_pack)                    # (Adam, repack, and the step's counters: nbt += 1, loss_sum += loss)
         self._ema_end_step()

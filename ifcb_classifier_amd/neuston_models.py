@@ -318,6 +318,11 @@ class NeustonModel(nn.Module):
         # reference hooks (training_step + a torch optimizer) write P from outside, which restarts the average
         ema = getattr(hparams, 'ema', None)
         self.ema = None if ema is None else float(ema)
+        # additive (TRAIN --clip-grad NORM): the engine clips the gradient by its global L2 norm inside its fused optimizer step, as
+        # torch.nn.utils.clip_grad_norm_(parameters, NORM) ahead of optimizer.step() / Lightning's gradient_clip_val.  Absent (older
+        # files) = off.  The fused path only: the reference hooks (training_step + a torch optimizer) leave clipping to their caller
+        cg = getattr(hparams, 'clip_grad', None)
+        self.clip_grad = None if cg is None else float(cg)
         # additive (TRAIN --distill TEACHER.ptl): the fused train loss is Hinton's, against the scores of a trained teacher that
         # ``attach_teacher`` hands over (TRAIN does; nothing else opens the file: RUN and the ONNX export need the student alone).
         # Absent (older files) = off.  The fused path only: ``self.criterion`` below stays the hard loss
@@ -333,6 +338,7 @@ class NeustonModel(nn.Module):
                                          class_weights=cw, weight_decay=float(getattr(hparams, 'weight_decay', None) or 0.0),
                                          label_smoothing=ls, focal_gamma=fg, mix=self.mixup > 0 or self.cutmix > 0,
                                          **({} if self.ema is None else {'ema_decay': self.ema}),
+                                         **({} if self.clip_grad is None else {'clip_grad': self.clip_grad}),
                                          **({} if self.distill is None else {'distill': self.distill}))
         # what upstream would have written at neuston_models.py:55; the engine's fused loss ops compute the same weighted, smoothed mean
         eng = self.model.engine
@@ -657,6 +663,15 @@ class NeustonModel(nn.Module):
         v = float(eng.loss_sum.item())
         eng.loss_sum.zero_()
         return v
+
+    def epoch_clip_stats(self):
+        """TRAIN --clip-grad: (the epoch's largest gradient norm before clipping, its clipped steps), read and restarted; None without"""
+        eng = self.model.engine
+        if getattr(eng, 'clip_state', None) is None:
+            return None
+        _norm, _coef, top, clipped = eng.grad_clip_stats()
+        eng.reset_grad_clip_stats()
+        return top, clipped
 
     # Validation #
     def validation_step(self, batch, batch_idx):

@@ -97,6 +97,13 @@ def _ema_decay(text):
     return v
 
 
+def _clip_grad(text):
+    v = float(text)
+    if not 0.0 < v < float('inf'):             # (nan fails both comparisons)
+        raise argparse.ArgumentTypeError('NORM must be finite and > 0, got %r' % text)
+    return v
+
+
 class _ExclusiveLossScalar(argparse.Action):
     """stores --label-smoothing / --focal-gamma (and --mixup / --cutmix / --distill); the second of the two to arrive non-zero is an
     argparse error naming both, as is --focal-gamma, --mixup or --cutmix beside --distill"""
@@ -258,13 +265,21 @@ class Trainer:
             ttf, vtf = train_loader.dataset.transforms, val_loader.dataset.transforms
             # one batch of look-ahead: upload + on-GPU preprocessing of batch k+1 run on a side stream beside step k
             n_next = None
+            epoch_steps = 0
             for (rois, targets, paths), nxt in self._lookahead(train_loader):
                 n = self._stage(model, rois, ttf, targets, train=True) if n_next is None else n_next
                 model.use_staged()
                 n_next = self._stage(model, nxt[0], ttf, nxt[1], train=True) if nxt is not None else None
                 model.fit_current(n, self.world, self._allreduce if self.world > 1 else None)
                 global_step += 1
+                epoch_steps += 1
             model.agg_train_loss = model.epoch_train_loss()
+            # TRAIN --clip-grad: the epoch's report, read where the loss sum is read (the epoch's one wait on the device) and restarted.
+            # Data parallel: every rank clips the same averaged gradient by the same norm, so rank 0 speaks for all
+            clip = model.epoch_clip_stats()
+            if clip is not None and self.rank == 0:
+                print('Epoch {}: largest gradient norm before clipping {:.4g} (--clip-grad {:g}): clipped {} of {} steps'.format(
+                    epoch, clip[0], model.clip_grad, clip[1], epoch_steps))
             # TRAIN --ema: the averaged model stands in P / RB from here to the checkpoint -- val_loss, F1 and the results files, early
             # stopping, the choice of the best epoch and the state_dict saved for it are the averaged model's; training goes on from the
             # raw weights.  Data parallel: every rank holds the same P after the exchange, so the same average; it is never communicated
@@ -745,6 +760,7 @@ def argparse_nn_train(train_subparser):
     optim.add_argument('--label-smoothing', metavar='EPS', default=0.0, type=_label_smoothing, action=_ExclusiveLossScalar, help='Label smoothing of the loss, as nn.CrossEntropyLoss(label_smoothing=EPS): the target distribution is (1-EPS) one-hot + EPS/C uniform, for noisy annotations. A float in [0, 1]; val_loss follows the smoothed value. Default is 0 (hard labels)')
     optim.add_argument('--focal-gamma', metavar='GAMMA', default=0.0, type=_focal_gamma, action=_ExclusiveLossScalar, help='Focal loss against class imbalance: the loss of an image is scaled by (1 - p)^GAMMA, p the softmax probability of its class, so images the network already classifies confidently count less. A finite float >= 0; composes with --class-norm (its weights are the per-class alpha), not with --label-smoothing; val_loss follows the focal value. Default is 0 (cross-entropy)')
     optim.add_argument('--ema', metavar='DECAY', type=_ema_decay, default=None, help='(MI355X path, additive) Keep an exponential moving average of the weights and of the BatchNorm running statistics, updated inside the fused optimizer step: avg += (1 - d) * (weights - avg) after every step, d = min(DECAY, (1 + t) / (10 + t)) at the t-th step (the warm-up of TensorFlow\'s ExponentialMovingAverage), as torch.optim.swa_utils.get_ema_multi_avg_fn / timm\'s ModelEmaV3. Validation (val_loss, F1, --results files), early stopping, the choice of the best epoch, the saved model and --onnx then use the averaged weights; the training trajectory is unchanged. A float in (0, 1), e.g. 0.999. Default (unset) is no averaging')
+    optim.add_argument('--clip-grad', metavar='NORM', type=_clip_grad, default=None, help='(MI355X path, additive) Clip the gradient of every step by its global L2 norm: when the norm over all parameters exceeds NORM the whole gradient is scaled by NORM / (norm + 1e-6), as torch.nn.utils.clip_grad_norm_(parameters, NORM) before every optimizer step / Lightning\'s gradient_clip_val. The norm and the scale are taken on the GPU inside the fused step; weight decay is added to the clipped gradient; with several GPUs the averaged gradient is clipped. Each epoch reports its largest norm and how many steps were clipped. A finite float > 0, e.g. 1.0. Default (unset) is no clipping')
     optim.add_argument('--distill', metavar='TEACHER.ptl', default=None, action=_ExclusiveLossScalar, help='(MI355X path, additive) Knowledge distillation: train MODEL to match the class scores of a trained teacher model file as well as the labels, (1 - A) * CrossEntropy + A * T^2 * KL(softmax(teacher / T) || softmax(student / T)). The teacher may be any backbone and input size (e.g. an inception_v3 teacher for a resnet18 student); its class list must equal the training set\'s. It sees every training batch with the same flips, turns and jitter, resized and normalised as it was trained. Composes with --class-norm (hard term only) and --label-smoothing, not with --focal-gamma, --mixup or --cutmix; val_loss stays the hard loss. RUN needs the student file alone. Default (unset) is no teacher')
     optim.add_argument('--distill-alpha', metavar='A', type=_distill_alpha, default=0.5, help='Weight of the teacher term of --distill, a float in [0, 1]. Default is 0.5')
     optim.add_argument('--distill-temperature', metavar='T', type=_distill_temperature, default=4.0, help='Softmax temperature of --distill, a finite float > 0. Default is 4')

@@ -792,13 +792,19 @@ class PlanBuilder:
         # the weight average (TRAIN --ema) is one more operand of the optimizer op, behind those of the plain step: E at the offset of P
         # (every bucket's op carries its slice); its weight is stamped per step (_set_update).  Without it the tuples are what they were
         ema = (_vp(e.E),) if e.ema_decay is not None else ()
+        # the clip state (TRAIN --clip-grad) is the operand behind the average, with max_norm as the scalar behind the average's weight:
+        # the op then takes the norm of the whole of G (ifcbk_grad_norm) ahead of its update.  Without it the tuples are what they were
+        clip, clipf = (), ()
+        if e.clip_grad is not None:
+            clip = (None,) * (1 - len(ema)) + (_vp(e.clip_state),)
+            clipf = (0.0, e.clip_grad)
         if e.optimizer == 'sgd':
             # additive option (north_star "SGD/Adam step"; upstream only has Adam): torch.optim.SGD's update, momentum buffer = M
-            opt.add(_lib.OP_SGD, 'sgd', p=(_vp(e.P), _vp(e.G), _vp(e.M) if e.momentum else None) + ema,
-                    i=(e.nparam_padded, 1), f=(e.lr, e.momentum, e.weight_decay, 1.0))
+            opt.add(_lib.OP_SGD, 'sgd', p=(_vp(e.P), _vp(e.G), _vp(e.M) if e.momentum else None) + ema + clip,
+                    i=(e.nparam_padded, 1), f=(e.lr, e.momentum, e.weight_decay, 1.0) + clipf)
         else:
-            opt.add(_lib.OP_ADAM, 'adam', p=(_vp(e.P), _vp(e.G), _vp(e.M), _vp(e.V)) + ema,
-                    i=(e.nparam_padded, 1), f=(e.lr, e.betas[0], e.betas[1], e.eps, e.weight_decay, 1.0))
+            opt.add(_lib.OP_ADAM, 'adam', p=(_vp(e.P), _vp(e.G), _vp(e.M), _vp(e.V)) + ema + clip,
+                    i=(e.nparam_padded, 1), f=(e.lr, e.betas[0], e.betas[1], e.eps, e.weight_decay, 1.0) + clipf)
         return opt
 
     def _assemble(self):
@@ -874,10 +880,13 @@ class PlanBuilder:
         complete it -- and behind the last input-gradient op that reads a bf16 shadow of the bucket (the shadow is rewritten by the
         repack) -- so that only the last bucket (the stem: 4 % of the parameters) is updated behind the end of backward.  Same
         arithmetic per element as one launch over the whole buffer (Adam / SGD are element-wise; the step count is a launch
-        argument of every bucket's op).  One launch at the end (IFCBK_OPT_BUCKETS <= 1, or no cut to be had): the three lists as given"""
+        argument of every bucket's op).  One launch at the end (IFCBK_OPT_BUCKETS <= 1, or no cut to be had): the three lists as given.
+        With clipping (TRAIN --clip-grad) it is the one launch at the end as well: the coefficient of every element's update is a
+        function of the norm of ALL of G, which exists only behind the last backward op, so no bucket can be updated beside backward
+        (a per-bucket sum of squares beside backward, with only the update at the end, would win the norm's pass back: not done)"""
         e = self.e
         whole = (bwd, opt, e._pack_multi(pack_ops))
-        if self.opt_buckets <= 1:
+        if self.opt_buckets <= 1 or e.clip_grad is not None:
             return whole
         from .dp import segment_plan
         offs = [e._op_param_offsets(o) for o in bwd.ops]

@@ -307,6 +307,35 @@ IFCBK_API int ifcbk_adam_ema_flat(ifcbk_ctx*, float* p, const float* g, float* m
                     void* stream);
 IFCBK_API int ifcbk_sgd_ema_flat(ifcbk_ctx*, float* p, const float* g, float* mom, float* ema /*nullable*/, int64_t n, float lr,
                    float momentum, float weight_decay, float grad_scale, float ema_w, void* stream);
+/* Global gradient-norm clipping (TRAIN --clip-grad): torch.nn.utils.clip_grad_norm_(parameters, max_norm), i.e. Lightning's
+ * gradient_clip_val, on the flat gradient.  ifcbk_grad_norm takes sum g^2 over n fp32 elements (g 16-byte aligned; n == 0 is legal: norm
+ * 0, coef 1) and leaves in `state`, a caller-allocated, 16-byte aligned device array of ifcbk_grad_clip_state_floats() floats:
+ *   state[0] = norm = grad_scale * sqrt(sum g^2): the norm of the gradient the optimizer sees (1 / world included);
+ *   state[1] = coef = min(1, max_norm / (norm + 1e-6)), torch's formula evaluated in fp32 on the fp32 norm the way a torch tensor
+ *              evaluates it, as fl(fl(1 / fl(norm + 1e-6)) * max_norm): the bits torch's clip_coef has for that norm;
+ *   state[2] = max(state[2], norm) and state[3] += (coef < 1): running figures, which the caller zeroes when it wants them restarted;
+ *   state[4...]: the partial sums of this call, one double per block (scratch: all written before any is read).
+ * A non-finite norm is not special-cased, as torch's default error_if_nonfinite=False: an inf in g gives norm inf and coef 0, a NaN
+ * gives norm NaN and coef NaN (the update then writes NaN); neither moves state[2] or state[3] except that inf becomes the maximum.
+ * Geometry (fixed, whatever n is): B = (ifcbk_grad_clip_state_floats() - 4) / 2 blocks of 256 threads, one 16-byte load per thread and
+ * pass, so one pass of the grid covers B * 1024 elements; a thread adds its squares in fp32 (four chains, one per component of its
+ * float4s; the n % 4 tail goes to the first thread), everything behind the thread is fp64 in a fixed order: the same g and n give the
+ * same bits on every call, no atomics.  Nothing is waited for: the state is read by the optimizer kernels below, on the device.
+ * IFCBK_EINVAL (nothing is launched, the state keeps its bits): NULL g or state, g or state not 16-byte aligned, n < 0, max_norm or
+ * grad_scale not finite or not > 0.                                                                                              */
+IFCBK_API size_t ifcbk_grad_clip_state_floats(void);
+IFCBK_API int ifcbk_grad_norm(ifcbk_ctx*, const float* g, int64_t n, float grad_scale, float max_norm, float* state, void* stream);
+/* The optimizer steps with clipping: clip_state != NULL runs ifcbk_grad_norm over the same g, n and grad_scale, then the update with
+ * grad_scale * state[1] (one fp32 product, formed in the kernel) where the plain step uses grad_scale: coef == 1 leaves the step's
+ * bits alone, grad_scale == 1 makes the scale coef itself.  Weight decay is added to the clipped gradient, as torch does (clipping
+ * scales .grad, the optimizer adds wd * p).  clip_state == NULL is ifcbk_adam_ema_flat / ifcbk_sgd_ema_flat, bit for bit (they are this
+ * call, and so are ifcbk_adam_flat / ifcbk_sgd_flat); max_norm is then not read.                                                   */
+IFCBK_API int ifcbk_adam_clip_flat(ifcbk_ctx*, float* p, const float* g, float* m, float* v, float* ema /*nullable*/, int64_t n, float lr,
+                    float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale, float ema_w,
+                    float max_norm, float* clip_state /*nullable*/, void* stream);
+IFCBK_API int ifcbk_sgd_clip_flat(ifcbk_ctx*, float* p, const float* g, float* mom, float* ema /*nullable*/, int64_t n, float lr,
+                   float momentum, float weight_decay, float grad_scale, float ema_w, float max_norm, float* clip_state /*nullable*/,
+                   void* stream);
 /* the plain update e[i] <- e[i] + w * (x[i] - e[i]) over n fp32 elements, for what no optimizer kernel streams (the BatchNorm running
  * statistics).  e and x 16-byte aligned; IFCBK_EINVAL: NULL e or x, n < 0, w outside [0, 1] or NaN.  w == 0 or n == 0 launch nothing. */
 IFCBK_API int ifcbk_ema_flat(ifcbk_ctx*, float* e, const float* x, int64_t n, float w, void* stream);
@@ -520,7 +549,9 @@ enum {
     IFCBK_OP_SGD,            /* p: P, G, momentum buffer (nullable); i[0] = n; f: lr, momentum, weight decay, grad scale.
                               * p[3] = the weight average's slice (nullable), f[4] = ema_w: ifcbk_sgd_ema_flat.  IFCBK_OP_ADAM (p: P, G, M,
                               * V; i: n, step; f: lr, beta1, beta2, eps, weight decay, grad scale) takes them as p[4] and f[6]:
-                              * ifcbk_adam_ema_flat.  NULL, what a zeroed op holds, is the step without an average                */
+                              * ifcbk_adam_ema_flat.  NULL, what a zeroed op holds, is the step without an average.
+                              * p[4] = the clip state (nullable), f[5] = max_norm: ifcbk_sgd_clip_flat; IFCBK_OP_ADAM takes them as p[5] and
+                              * f[7]: ifcbk_adam_clip_flat.  NULL, what a zeroed op holds, is the step without clipping              */
     IFCBK_OP_RETIRED_31,     /* retired (was the per-chunk-table dgrad + BatchNorm-backward sums); the slot keeps the numbering */
     IFCBK_OP_BIAS_RELU_BWD,  /* p: y, dy, dz, dbias; u.bn: M, C, ldx = ld(y), ldy = ld(dy), relu, dtype; i[0] = ld(dz)          */
     IFCBK_OP_DROPOUT,        /* p: x, mask (nullable), y; i[0] = n, i[1] = dtype; f[0] = scale; flags bit 0 accumulate           */
