@@ -14,6 +14,7 @@ import pytest
 import torch
 
 import clip_cases as cc
+from option_matrix import bits as _bits, real_mask as _real_mask, reset as _reset, same      # noqa: F401  (moved there, unchanged)
 
 pytestmark = pytest.mark.gpu
 
@@ -27,31 +28,6 @@ def _engine(name, b, **kw):
     eng = Engine(graph.build(name, NC, pretrained=False), device=0, max_batch=b, **kw)
     _reset(eng)
     return eng
-
-
-def _reset(eng, seed=4321):
-    eng.init_weights(seed=seed)
-    eng.M.zero_()
-    eng.V.zero_()
-    eng.G.zero_()
-    eng.RB.zero_()
-    for k, v in eng.bviews.items():
-        if k.endswith('running_var'):
-            v.fill_(1.0)
-    eng.nbt.zero_()
-    eng.loss_sum.zero_()
-    eng.step_count = 0
-    eng.dropout_seed, eng.dropout_calls = 5, 0
-    if eng.clip_state is not None:
-        eng.clip_state.zero_()
-
-
-def _bits(t):
-    return t.detach().cpu().contiguous().view(torch.int32 if t.dtype == torch.float32 else t.dtype)
-
-
-def same(a, b):
-    return torch.equal(_bits(a), _bits(b))
 
 
 def _snap(eng):
@@ -133,13 +109,6 @@ def test_a_bound_nothing_reaches_leaves_the_steps_bits_alone(rig, mode):
             assert same(got[key], want[k][key]), (mode, k, key)
     norm, coef, top, clipped = rig.loose.grad_clip_stats()
     assert coef == 1.0 and clipped == 0 and 0.0 < norm <= top < math.inf
-
-
-def _real_mask(eng):
-    real = torch.zeros(eng.nparam_padded, dtype=torch.bool)
-    for key, (o, n, _shape, _kind, _node) in eng.poff.items():
-        real[o:o + n] = True
-    return real
 
 
 def _check_padding_is_zero(eng):

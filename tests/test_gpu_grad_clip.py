@@ -17,6 +17,7 @@ import torch
 
 import clip_cases as cc
 import op_bounds as ob
+import option_matrix as om
 
 pytestmark = pytest.mark.gpu
 
@@ -250,26 +251,14 @@ def test_adam_clip_flat(ctx, n, ema, gs):
 
 
 def _scale_delta(n):
-    """how far, relatively, the device's clipped gradient g * fl(gs * coef) may lie from the reference's fl(gs * g * max / (norm + 1e-6))
-    (formed in float64, rounded once): the norm's bound of tests/clip_cases.py, and one rounding each for norm + 1e-6, the reciprocal, its
-    product with max_norm, the product gs * coef, the kernel's product with g and the reference's rounding"""
-    blocks = cc.geometry(_lib().load())[0]
-    return ((cc.chain(n, blocks) + 6) / 2.0 + 2.0 + 6.0) * cc.U
+    return om.scale_delta(n, cc.geometry(_lib().load())[0])
 
 
 def _reference_gradient(host, gs, mx):
-    """clip_grad_norm_ on the CPU, on the float64 product grad_scale * g, rounded once to the fp32 gradient torch.optim then takes"""
-    _total, (gc,) = cc.torch_clip([host[1].double() * float(np.float32(gs))], mx)
-    return gc.float()
+    return om.reference_gradient(host[1], gs, mx)
 
 
-def _sensitivity(step_fn, gc, delta):
-    """how far the float64 result moves when every gradient element moves by delta relatively, to first order, doubled: the larger of the
-    two one-sided differences of the oracle, times 2"""
-    w0 = step_fn(gc)['p'][0]
-    up = step_fn((gc.double() * (1 + delta)))['p'][0]
-    dn = step_fn((gc.double() * (1 - delta)))['p'][0]
-    return 2 * torch.maximum((up - w0).abs(), (dn - w0).abs())
+_sensitivity = om.sensitivity                          # (the three live in tests/option_matrix.py now, with their docstrings)
 
 
 def _torch_adam(host, n, gs, mx, wd, step):
