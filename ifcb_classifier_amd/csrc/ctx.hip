@@ -6,6 +6,24 @@
 #include <string.h>
 #include <unistd.h>
 
+// Operand slots of the op kinds with optional operands (the layout blocks at IFCBK_OP_SOFTMAX_XENT, IFCBK_OP_ADAM and IFCBK_OP_SGD in
+// include/ifcbk.h): a NULL pointer or a zero scalar, what a zeroed op holds, is the option switched off.
+enum {  // IFCBK_OP_SOFTMAX_XENT and IFCBK_OP_SOFTMAX_XENT_W
+    LOSS_LOGITS, LOSS_TARGET, LOSS_LOSS, LOSS_DLOGITS, LOSS_CLASS_WEIGHT, LOSS_LAM, LOSS_TEACHER,                  // p[]
+    LOSS_N = 0, LOSS_NC,                                                                                           // i[]
+    LOSS_WEIGHT = 0, LOSS_SMOOTHING, LOSS_GAMMA, LOSS_ALPHA, LOSS_TEMPERATURE                                      // f[]
+};
+enum {  // IFCBK_OP_ADAM
+    ADAM_P, ADAM_G, ADAM_M, ADAM_V, ADAM_E, ADAM_CLIP_STATE,                                                       // p[]
+    ADAM_N = 0, ADAM_STEP,                                                                                         // i[]
+    ADAM_LR = 0, ADAM_BETA1, ADAM_BETA2, ADAM_EPS, ADAM_WEIGHT_DECAY, ADAM_GRAD_SCALE, ADAM_EMA_W, ADAM_MAX_NORM   // f[]
+};
+enum {  // IFCBK_OP_SGD
+    SGD_P, SGD_G, SGD_M, SGD_E, SGD_CLIP_STATE,                                                                    // p[]
+    SGD_N = 0,                                                                                                     // i[]
+    SGD_LR = 0, SGD_MOMENTUM, SGD_WEIGHT_DECAY, SGD_GRAD_SCALE, SGD_EMA_W, SGD_MAX_NORM                            // f[]
+};
+
 // IFCBK_SEGV_BACKTRACE=1: print the host call stack (frames of this library and of the HIP runtime) when the process takes a
 // SIGSEGV / SIGABRT, then die with the default action.  Diagnostic only (used to locate the runtime call that faults in a
 // multi-stream hipGraph capture); async-signal-safe calls only: backtrace_symbols_fd writes straight to stderr.
@@ -131,53 +149,33 @@ extern "C" int ifcbk_ctx_live_graphs(ifcbk_ctx* c) { return c ? c->n_graphs : 0;
 
 extern "C" const char* ifcbk_last_error(ifcbk_ctx* c) { return c ? c->err : g_create_err; }
 
-// the weight average's slice of an optimizer op (TRAIN --ema): the operand behind those of the plain step, p[4] of IFCBK_OP_ADAM (its
-// weight: f[6]) and p[3] of IFCBK_OP_SGD (f[4]); NULL, what a zeroed op holds, is the step without an average
-static float* op_ema(const ifcbk_op* o) { return (float*)o->p[o->kind == IFCBK_OP_ADAM ? 4 : 3]; }
-// the clip state of an optimizer op (TRAIN --clip-grad), the operand behind the average: p[5] of IFCBK_OP_ADAM (max_norm: f[7]) and p[4]
-// of IFCBK_OP_SGD (f[5]); NULL, what a zeroed op holds, is the step without clipping
-static float* op_clip(const ifcbk_op* o) { return (float*)o->p[o->kind == IFCBK_OP_ADAM ? 5 : 4]; }
+// the two loss kinds: which kernel the optional operands select, and the combinations that are refused
+static int run_loss(ifcbk_ctx* c, const ifcbk_op* o, void* st) {
+    void* const* p = o->p;
+    const float *logits = (const float*)p[LOSS_LOGITS], *lam = (const float*)p[LOSS_LAM], *teacher = (const float*)p[LOSS_TEACHER];
+    const float* class_weight = o->kind == IFCBK_OP_SOFTMAX_XENT_W ? (const float*)p[LOSS_CLASS_WEIGHT] : nullptr;
+    const int64_t* target = (const int64_t*)p[LOSS_TARGET];
+    float *loss = (float*)p[LOSS_LOSS], *dlogits = (float*)p[LOSS_DLOGITS];
+    const int N = (int)o->i[LOSS_N], NC = (int)o->i[LOSS_NC], acc = o->flags & 1;
+    const float weight = o->f[LOSS_WEIGHT], smoothing = o->f[LOSS_SMOOTHING], gamma = o->f[LOSS_GAMMA];
+    if (smoothing != 0.f && gamma != 0.f)
+        IFCBK_FAIL(c, IFCBK_EINVAL, "softmax_xent op: label smoothing (f[1]) and focal gamma (f[2]) are both set");
+    if (teacher && gamma != 0.f) IFCBK_FAIL(c, IFCBK_EINVAL, "softmax_xent op: teacher logits (p[6]) and focal gamma (f[2]) are both set");
+    if (teacher && lam) IFCBK_FAIL(c, IFCBK_EINVAL, "softmax_xent op: teacher logits (p[6]) and mix factors (p[5]) are both set");
+    if (lam && gamma != 0.f) IFCBK_FAIL(c, IFCBK_EINVAL, "softmax_xent op: mix factors (p[5]) and focal gamma (f[2]) are both set");
+    if (teacher)
+        return ifcbk_softmax_xent_distill(c, logits, target, teacher, class_weight, N, NC, weight, smoothing, o->f[LOSS_ALPHA],
+                                          o->f[LOSS_TEMPERATURE], loss, acc, dlogits, st);
+    if (lam) return ifcbk_softmax_xent_mix(c, logits, target, lam, class_weight, N, NC, weight, smoothing, loss, acc, dlogits, st);
+    if (smoothing != 0.f) return ifcbk_softmax_xent_ls(c, logits, target, class_weight, N, NC, weight, smoothing, loss, acc, dlogits, st);
+    if (gamma != 0.f) return ifcbk_softmax_xent_focal(c, logits, target, class_weight, N, NC, weight, gamma, loss, acc, dlogits, st);
+    if (o->kind == IFCBK_OP_SOFTMAX_XENT_W) return ifcbk_softmax_xent_w(c, logits, target, class_weight, N, NC, weight, loss, acc, dlogits, st);
+    return ifcbk_softmax_xent(c, logits, target, N, NC, weight, loss, acc, dlogits, st);
+}
 
 static int run_one(ifcbk_ctx* c, const ifcbk_op* o, void* st) {
     void* const* p = o->p;
     const int acc = o->flags & 1, pacc = (o->flags >> 1) & 1;
-    // a clip state (TRAIN --clip-grad) rides on the two optimizer kinds: NULL, what a zeroed op holds, takes the cases below untouched;
-    // a state sends the op to the clipping entry points with the same operands and max_norm from f[7] / f[5]
-    if (o->kind == IFCBK_OP_ADAM && op_clip(o))
-        return ifcbk_adam_clip_flat(c, (float*)p[0], (const float*)p[1], (float*)p[2], (float*)p[3], op_ema(o), o->i[0], o->f[0], o->f[1],
-                                    o->f[2], o->f[3], o->f[4], (int)o->i[1], o->f[5], o->f[6], o->f[7], op_clip(o), st);
-    if (o->kind == IFCBK_OP_SGD && op_clip(o))
-        return ifcbk_sgd_clip_flat(c, (float*)p[0], (const float*)p[1], (float*)p[2], op_ema(o), o->i[0], o->f[0], o->f[1], o->f[2],
-                                   o->f[3], o->f[4], o->f[5], op_clip(o), st);
-    // label smoothing (TRAIN --label-smoothing) rides on the two loss kinds: f[1] != 0 is the smoothing factor and goes to the smoothed
-    // kernel, with p[4] as the class weights of the _W kind and none for the plain kind; f[1] == 0 takes the cases below untouched
-    if ((o->kind == IFCBK_OP_SOFTMAX_XENT || o->kind == IFCBK_OP_SOFTMAX_XENT_W) && o->f[1] != 0.f && o->f[2] != 0.f)
-        IFCBK_FAIL(c, IFCBK_EINVAL, "softmax_xent op: label smoothing (f[1]) and focal gamma (f[2]) are both set");
-    // a teacher's logits (TRAIN --distill) ride on them as p[6], with alpha in f[3] and the temperature in f[4]: NULL, what a zeroed op
-    // holds, is every case below untouched; an array sends the op to the distillation kernel with f[1] as its smoothing factor; it
-    // combines with neither focal loss nor a mixed batch
-    if ((o->kind == IFCBK_OP_SOFTMAX_XENT || o->kind == IFCBK_OP_SOFTMAX_XENT_W) && p[6]) {
-        if (o->f[2] != 0.f) IFCBK_FAIL(c, IFCBK_EINVAL, "softmax_xent op: teacher logits (p[6]) and focal gamma (f[2]) are both set");
-        if (p[5]) IFCBK_FAIL(c, IFCBK_EINVAL, "softmax_xent op: teacher logits (p[6]) and mix factors (p[5]) are both set");
-        return ifcbk_softmax_xent_distill(c, (const float*)p[0], (const int64_t*)p[1], (const float*)p[6],
-                                          o->kind == IFCBK_OP_SOFTMAX_XENT_W ? (const float*)p[4] : nullptr, (int)o->i[0], (int)o->i[1], o->f[0],
-                                          o->f[1], o->f[3], o->f[4], (float*)p[2], acc, (float*)p[3], st);
-    }
-    // the factors of a mixed batch (TRAIN --mixup / --cutmix) ride on them as p[5]: NULL, what a zeroed op holds, is every case below
-    // untouched; an array sends the op to the two-target kernel with f[1] as its smoothing factor; it does not combine with focal loss
-    if ((o->kind == IFCBK_OP_SOFTMAX_XENT || o->kind == IFCBK_OP_SOFTMAX_XENT_W) && p[5]) {
-        if (o->f[2] != 0.f) IFCBK_FAIL(c, IFCBK_EINVAL, "softmax_xent op: mix factors (p[5]) and focal gamma (f[2]) are both set");
-        return ifcbk_softmax_xent_mix(c, (const float*)p[0], (const int64_t*)p[1], (const float*)p[5],
-                                      o->kind == IFCBK_OP_SOFTMAX_XENT_W ? (const float*)p[4] : nullptr, (int)o->i[0], (int)o->i[1], o->f[0], o->f[1],
-                                      (float*)p[2], acc, (float*)p[3], st);
-    }
-    if ((o->kind == IFCBK_OP_SOFTMAX_XENT || o->kind == IFCBK_OP_SOFTMAX_XENT_W) && o->f[1] != 0.f)
-        return ifcbk_softmax_xent_ls(c, (const float*)p[0], (const int64_t*)p[1], o->kind == IFCBK_OP_SOFTMAX_XENT_W ? (const float*)p[4] : nullptr,
-                                     (int)o->i[0], (int)o->i[1], o->f[0], o->f[1], (float*)p[2], acc, (float*)p[3], st);
-    // focal loss (TRAIN --focal-gamma) rides on them the same way: f[2] != 0 is gamma and goes to the focal kernel; the two do not combine
-    if ((o->kind == IFCBK_OP_SOFTMAX_XENT || o->kind == IFCBK_OP_SOFTMAX_XENT_W) && o->f[2] != 0.f)
-        return ifcbk_softmax_xent_focal(c, (const float*)p[0], (const int64_t*)p[1], o->kind == IFCBK_OP_SOFTMAX_XENT_W ? (const float*)p[4] : nullptr,
-                                        (int)o->i[0], (int)o->i[1], o->f[0], o->f[2], (float*)p[2], acc, (float*)p[3], st);
     switch (o->kind) {
         case IFCBK_OP_CONV_FWD: return ifcbk_conv2d_fwd(c, &o->u.conv, p[0], p[1], p[2], (float*)p[3], st);
         case IFCBK_OP_CONV_FWD_AFFINE:
@@ -249,19 +247,18 @@ static int run_one(ifcbk_ctx* c, const ifcbk_op* o, void* st) {
         case IFCBK_OP_HEAD_BWD:
             return ifcbk_head_bwd(c, &o->u.head, (const float*)p[0], (const float*)p[1], (const uint8_t*)p[2],
                                   (const float*)p[3], (float*)p[4], (float*)p[5], p[6], (int)o->i[0], pacc, st);
-        case IFCBK_OP_SOFTMAX_XENT:
-            return ifcbk_softmax_xent(c, (const float*)p[0], (const int64_t*)p[1], (int)o->i[0], (int)o->i[1], o->f[0],
-                                      (float*)p[2], acc, (float*)p[3], st);
-        case IFCBK_OP_SOFTMAX_XENT_W:
-            return ifcbk_softmax_xent_w(c, (const float*)p[0], (const int64_t*)p[1], (const float*)p[4], (int)o->i[0], (int)o->i[1], o->f[0],
-                                        (float*)p[2], acc, (float*)p[3], st);
+        case IFCBK_OP_SOFTMAX_XENT: case IFCBK_OP_SOFTMAX_XENT_W: return run_loss(c, o, st);
         case IFCBK_OP_SOFTMAX: return ifcbk_softmax(c, (const float*)p[0], (int)o->i[0], (int)o->i[1], (float*)p[1], st);
+        // (a NULL weight average or clip state is the step without it: ifcbk_adam_flat / ifcbk_sgd_flat are these calls)
         case IFCBK_OP_ADAM:
-            return ifcbk_adam_ema_flat(c, (float*)p[0], (const float*)p[1], (float*)p[2], (float*)p[3], op_ema(o), o->i[0], o->f[0],
-                                       o->f[1], o->f[2], o->f[3], o->f[4], (int)o->i[1], o->f[5], o->f[6], st);
+            return ifcbk_adam_clip_flat(c, (float*)p[ADAM_P], (const float*)p[ADAM_G], (float*)p[ADAM_M], (float*)p[ADAM_V], (float*)p[ADAM_E],
+                                        o->i[ADAM_N], o->f[ADAM_LR], o->f[ADAM_BETA1], o->f[ADAM_BETA2], o->f[ADAM_EPS], o->f[ADAM_WEIGHT_DECAY],
+                                        (int)o->i[ADAM_STEP], o->f[ADAM_GRAD_SCALE], o->f[ADAM_EMA_W], o->f[ADAM_MAX_NORM],
+                                        (float*)p[ADAM_CLIP_STATE], st);
         case IFCBK_OP_SGD:
-            return ifcbk_sgd_ema_flat(c, (float*)p[0], (const float*)p[1], (float*)p[2], op_ema(o), o->i[0], o->f[0], o->f[1], o->f[2],
-                                      o->f[3], o->f[4], st);
+            return ifcbk_sgd_clip_flat(c, (float*)p[SGD_P], (const float*)p[SGD_G], (float*)p[SGD_M], (float*)p[SGD_E], o->i[SGD_N], o->f[SGD_LR],
+                                       o->f[SGD_MOMENTUM], o->f[SGD_WEIGHT_DECAY], o->f[SGD_GRAD_SCALE], o->f[SGD_EMA_W], o->f[SGD_MAX_NORM],
+                                       (float*)p[SGD_CLIP_STATE], st);
         case IFCBK_OP_MEMSET:
             IFCBK_HIP(c, hipMemsetAsync(p[0], (int)o->i[1], (size_t)o->i[0], (hipStream_t)st));
             return 0;
@@ -688,8 +685,8 @@ extern "C" int ifcbk_op_kernel(const ifcbk_op* o, char* name, size_t cap) {
         case IFCBK_OP_WEIGHT_PACK: snprintf(name, cap, "weight_pack_kernel"); break;
         case IFCBK_OP_WEIGHT_PACK_MULTI: snprintf(name, cap, "weight_pack_multi_kernel"); break;
         case IFCBK_OP_SOFTMAX_XENT: case IFCBK_OP_SOFTMAX_XENT_W:
-            if (o->p[6]) snprintf(name, cap, "softmax_xent_distill_kernel");
-            else if (o->p[5]) snprintf(name, cap, "softmax_xent_mix_kernel");     // (the one-target losses stay unnamed, as they were)
+            if (o->p[LOSS_TEACHER]) snprintf(name, cap, "softmax_xent_distill_kernel");
+            else if (o->p[LOSS_LAM]) snprintf(name, cap, "softmax_xent_mix_kernel");     // (the one-target losses stay unnamed, as they were)
             break;
         default: break;
     }
@@ -756,17 +753,19 @@ extern "C" int ifcbk_op_cost(const ifcbk_op* o, double* flops, double* bytes) {
             break;
         }
         // (+ the weight average: read and written; + the norm's pass over the gradient when the op clips)
-        case IFCBK_OP_ADAM: by = (double)o->i[0] * (28 + (o->p[4] ? 8 : 0) + (o->p[5] ? 4 : 0)); break;
-        case IFCBK_OP_SGD: by = (double)o->i[0] * ((o->p[2] ? 20 : 12) + (o->p[3] ? 8 : 0) + (o->p[4] ? 4 : 0)); break;
-        case IFCBK_OP_SOFTMAX_XENT: case IFCBK_OP_SOFTMAX_XENT_W:
-            if (o->p[6]) {                  // the distillation loss: logits and teacher in, dlogits out (when asked for), targets
-                fl = (double)o->i[0] * o->i[1] * 30;
-                by = (double)o->i[0] * o->i[1] * (o->p[3] ? 12 : 8) + (double)o->i[0] * 8;
-            } else if (o->p[5]) {           // the two-target loss: logits in, dlogits out (when asked for), targets and factors
-                fl = (double)o->i[0] * o->i[1] * 12;
-                by = (double)o->i[0] * o->i[1] * (o->p[3] ? 8 : 4) + (double)o->i[0] * 12;
+        case IFCBK_OP_ADAM: by = (double)o->i[ADAM_N] * (28 + (o->p[ADAM_E] ? 8 : 0) + (o->p[ADAM_CLIP_STATE] ? 4 : 0)); break;
+        case IFCBK_OP_SGD: by = (double)o->i[SGD_N] * ((o->p[SGD_M] ? 20 : 12) + (o->p[SGD_E] ? 8 : 0) + (o->p[SGD_CLIP_STATE] ? 4 : 0)); break;
+        case IFCBK_OP_SOFTMAX_XENT: case IFCBK_OP_SOFTMAX_XENT_W: {
+            const double N = (double)o->i[LOSS_N], NC = (double)o->i[LOSS_NC];
+            if (o->p[LOSS_TEACHER]) {       // the distillation loss: logits and teacher in, dlogits out (when asked for), targets
+                fl = N * NC * 30;
+                by = N * NC * (o->p[LOSS_DLOGITS] ? 12 : 8) + N * 8;
+            } else if (o->p[LOSS_LAM]) {    // the two-target loss: logits in, dlogits out (when asked for), targets and factors
+                fl = N * NC * 12;
+                by = N * NC * (o->p[LOSS_DLOGITS] ? 8 : 4) + N * 12;
             }
             break;
+        }
         default: break;
     }
     if (flops) *flops = fl;

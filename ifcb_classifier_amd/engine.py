@@ -12,9 +12,13 @@ import os
 
 import torch
 
-from . import _lib
+from . import _lib, ops
 from ._lib import Op, ConvDesc, BnDesc, PoolDesc, HeadDesc, RoiDesc, pad_fill
 from .plan import OpList, Program, PlanBuilder, schedule_lanes, _overlap, _vp       # noqa: F401  (re-exported: tests import them from here)
+
+# operand slots the engine reads back from ops of a plan
+_PACK_W_MASTER, _PACK_W, _PACK_WT, _PACK_WT_LD = (ops.slot(_lib.OP_WEIGHT_PACK, name) for name in ('w_master', 'w', 'wT', 'wT_ld'))
+_GROUP_N, _SEG_K = ops.slot(_lib.OP_CONV_WGRAD_GROUP, 'n'), ops.tail(_lib.OP_CONV_WGRAD_SEG, 'kseg')
 
 
 # environment switches the library reads at launch time that change a workspace size or a partial-row count (csrc/conv_*.hip,
@@ -99,6 +103,9 @@ class Engine:
         if str(optimizer).lower() not in ('adam', 'sgd'):
             raise ValueError("optimizer must be 'adam' (the reference's only behaviour, neuston_models.py:63-64) or 'sgd'")
         self.optimizer, self.momentum = str(optimizer).lower(), float(momentum)
+        # the slots _set_update stamps on every step, resolved once
+        opt_kind = _lib.OP_SGD if self.optimizer == 'sgd' else _lib.OP_ADAM
+        self._upd_step, self._upd_scale, self._upd_ema_w = (ops.slot(opt_kind, name) for name in ('step', 'grad_scale', 'ema_w'))
         # additive options (TRAIN --weight-decay / --class-norm; upstream has neither): torch's L2 form g + wd * p in the fused
         # Adam / SGD kernels, and per-class weights of the loss (nn.CrossEntropyLoss(weight=...)); None / 0.0: upstream's behaviour
         self.weight_decay = float(weight_decay or 0.0)
@@ -132,7 +139,7 @@ class Engine:
         # plans, op tables and launches are what they were
         self.distill = check_distill(distill, self.focal_gamma, self.mix)
         # additive (TRAIN --ema): an exponential moving average E / ERB of the parameters P and the BatchNorm running statistics RB, taken
-        # inside the optimizer ops (their p[4] / p[3]) and by one ifcbk_ema_flat call per step; ema_weights() evaluates and exports it.
+        # inside the optimizer ops (their operand E) and by one ifcbk_ema_flat call per step; ema_weights() evaluates and exports it.
         # None: no shadow buffers, and plans, op tables and launches are what they were
         self.ema_decay = None if ema_decay is None else float(ema_decay)
         if self.ema_decay is not None and not 0.0 < self.ema_decay < 1.0:      # (a NaN fails both comparisons)
@@ -853,9 +860,9 @@ class Engine:
             for k, o in enumerate(pack.ops):
                 d = o.u.conv
                 it = items[k]
-                it.w_master, it.w, it.wT = o.p[0], o.p[1], o.p[2]
+                it.w_master, it.w, it.wT = o.p[_PACK_W_MASTER], o.p[_PACK_W], o.p[_PACK_WT]
                 it.K, it.RS, it.C, it.Cw = d.K, d.R * d.S, d.C, d.Cw
-                it.wT_ld = int(o.i[0])
+                it.wT_ld = int(o.i[_PACK_WT_LD])
                 it.first_block = blk
                 blk += ((d.K + 31) // 32) * d.R * d.S * ((d.C + 31) // 32)      # 32x32 (k, c) tiles per filter tap
             raw = np.frombuffer(bytes(items), dtype=np.uint8).copy()
@@ -870,28 +877,16 @@ class Engine:
 
     def _op_param_offsets(self, o):
         """element offsets (into the flat gradient buffer) of the parameter tensors a backward op writes."""
-        base = self.G.data_ptr()
-        if o.kind == _lib.OP_CONV_WGRAD:
-            return [(o.p[2] - base) // 4]
-        if o.kind == _lib.OP_STEM_U8_WGRAD:
-            return [(o.p[3] - base) // 4]
+        base, slots = self.G.data_ptr(), ops.PARAM_GRADS.get(o.kind, ())
+        # the counted kinds: as many gradients as the group has members, one per segment in use
         if o.kind == _lib.OP_CONV_WGRAD_GROUP:
-            return [(o.p[1 + k] - base) // 4 for k in range(int(o.i[0]))]
-        if o.kind == _lib.OP_CONV_WGRAD_SEG:
-            return [(o.p[2 + k] - base) // 4 for k in range(4) if o.i[k] > 0]
-        # (a vgg*_bn conv's bias rides with its BatchNorm's gradients: nothing writes it -- the batch mean absorbs the bias, its
-        # gradient is identically zero -- but the bucket plan must see the whole flat buffer covered)
-        if o.kind == _lib.OP_BN_BWD:
-            g0 = (o.p[8] - base) // 4
-            return [g0, (o.p[9] - base) // 4] + self.cbias_after.get(g0, [])
-        if o.kind in (_lib.OP_BN_BWD_MAXPOOL, _lib.OP_BN_BWD_PARTIALS):
-            g0 = (o.p[9] - base) // 4
-            return [g0, (o.p[10] - base) // 4] + self.cbias_after.get(g0, [])
-        if o.kind == _lib.OP_HEAD_BWD:
-            return [(o.p[4] - base) // 4, (o.p[5] - base) // 4] if o.p[4] else []
-        if o.kind == _lib.OP_BIAS_RELU_BWD:
-            return [(o.p[3] - base) // 4] if o.p[3] else []
-        return []
+            slots = slots[:int(o.i[_GROUP_N])]
+        elif o.kind == _lib.OP_CONV_WGRAD_SEG:
+            slots = [s for s, k in zip(slots, _SEG_K) if o.i[k] > 0]
+        offs = [(o.p[s] - base) // 4 for s in slots if o.p[s]]
+        # (a vgg*_bn conv's bias rides with its BatchNorm's gradients, the first of which cbias_after is keyed by: nothing writes it -- the
+        # batch mean absorbs the bias, its gradient is identically zero -- but the bucket plan must see the whole flat buffer covered)
+        return offs + self.cbias_after.get(offs[0], []) if offs else offs
 
     def ddp_segments(self, pl, nseg=8):
         """split the backward list into <= nseg runs whose finished gradients form a contiguous tail
@@ -1184,10 +1179,10 @@ class Engine:
     def _set_update(self, op, grad_scale=1.0):
         """per-step scalars of the optimizer op: the step count (Adam's bias correction), the gradient scale (1/world) and, with a
         weight average, the weight of this step's update (_ema_begin_step)"""
-        op.i[1] = self.step_count
-        op.f[3 if self.optimizer == 'sgd' else 5] = grad_scale
+        op.i[self._upd_step] = self.step_count
+        op.f[self._upd_scale] = grad_scale
         if self.ema_decay is not None:
-            op.f[4 if self.optimizer == 'sgd' else 6] = self._ema_w
+            op.f[self._upd_ema_w] = self._ema_w
 
     def adam_step(self, N):
         pl = self.plan(N)

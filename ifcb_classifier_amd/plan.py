@@ -5,7 +5,7 @@ emitters in reverse node order, assembly.  A builder lives for one ``Engine.plan
 import ctypes as C
 import os
 
-from . import _lib
+from . import _lib, ops
 from ._lib import Op, ConvDesc, BnDesc, PoolDesc, HeadDesc
 
 
@@ -13,9 +13,16 @@ def _vp(t, byte_off=0):
     return None if t is None else C.c_void_p(t.data_ptr() + byte_off)
 
 
+# operand slots the planner reads back from ops it has emitted
+_PACK_MASTER, _PACK_WT = (ops.slot(_lib.OP_WEIGHT_PACK, name) for name in ('w_master', 'wT'))
+_DGRAD_WT = {kind: ops.slot(kind, 'wT') for kind in (_lib.OP_CONV_DGRAD, _lib.OP_CONV_DGRAD_BNSTAT)}
+
+
 class OpList:
     """ops + tags + scheduling metadata: (lane, reads, writes) per op.  A resource is (key..., lo, hi): a channel range
-    of a tensor.  An op without annotations is a full barrier on lane 0 (loss, head, Adam, pack ...)."""
+    of a tensor.  An op without annotations is a full barrier on lane 0 (loss, head, Adam, pack ...).  ``add`` takes p, i and f each
+    as a tuple in the slot order of the kind's row in ops.OPERANDS or as a dict keyed by its slot names (an unknown name or a tuple
+    longer than the row raises; None or an absent name leaves the zero of a fresh op)."""
 
     def __init__(self):
         self.ops = []
@@ -25,13 +32,9 @@ class OpList:
     def add(self, kind, tag, p=(), i=(), f=(), flags=0, conv=None, bn=None, pool=None, head=None, lane=0, reads=None, writes=None):
         o = Op()
         o.kind, o.flags = kind, flags
-        self.meta.append((lane, reads, writes))
-        for k, v in enumerate(p):
-            o.p[k] = v if (v is None or isinstance(v, int)) else v.value
-        for k, v in enumerate(i):
-            o.i[k] = int(v)
-        for k, v in enumerate(f):
-            o.f[k] = float(v)
+        ops.fill(kind, 'p', o.p, p, lambda v: v if isinstance(v, int) else v.value)
+        ops.fill(kind, 'i', o.i, i, int)
+        ops.fill(kind, 'f', o.f, f, float)
         if conv is not None:
             o.u.conv = conv
         elif bn is not None:
@@ -42,6 +45,7 @@ class OpList:
             o.u.head = head
         self.ops.append(o)
         self.tags.append(tag)
+        self.meta.append((lane, reads, writes))
         return o
 
     def extend(self, other):
@@ -129,7 +133,7 @@ class Program:
         on the caller's stream (per-kernel durations without another lane's kernel sharing the GPU)"""
         arr = (Op * self.n)(*self.arr)
         for k in (range(self.n) if which is None else which):
-            arr[k].flags |= 0x80
+            arr[k].flags |= ops.FLAG_TIMED
         if single_lane:
             for k in range(self.n):
                 arr[k].flags &= 0xff
@@ -325,7 +329,7 @@ class PlanBuilder:
 
     def _acc(self, buf):
         """accumulate flag of a write into the gradient of `buf`: 0 for its first writer of this backward pass"""
-        a = 1 if buf.id in self.written else 0
+        a = ops.FLAG_ACC if buf.id in self.written else 0
         self.written.add(buf.id)
         return a
 
@@ -354,7 +358,7 @@ class PlanBuilder:
         pre, ldpre = e._pre_ptr(n)
         ppd = PoolDesc(self.N, cp.x.H, cp.x.W, n.K, ldpre, 3, 3, 1, 1, 1, 1, cp.P, cp.Q, n.y.buf.C, e.cdtype)
         self.fwd_e.add(_lib.OP_AVGPOOL_AFFINE, cp.name + '(' + n.name + ')', p=(pre, e._stat(n, 4), e._stat(n, 5), self._a(n.y)),
-                       flags=4 if n.relu else 0, pool=ppd, lane=lane, reads=[rpre(n)], writes=[ra(n.y)])
+                       flags=ops.FLAG_RELU if n.relu else 0, pool=ppd, lane=lane, reads=[rpre(n)], writes=[ra(n.y)])
 
     def _pack_op(self, n, d):
         """the weight_pack of a conv / plain layer: fp32 master -> shadow (and its transpose, where an input gradient reads one)"""
@@ -377,7 +381,7 @@ class PlanBuilder:
     def _eval_conv(self, n, d):
         """inference: eval-BN affine (+residual) + ReLU fused into the conv epilogue; no raw tensor"""
         e, lst, Le, g = self.e, self.fwd_e, self.lane_eval[n], n.group
-        relu, scale, shift = (4 if n.relu else 0), e._stat(n, 4), e._stat(n, 5)
+        relu, scale, shift = (ops.FLAG_RELU if n.relu else 0), e._stat(n, 4), e._stat(n, 5)
         if g is not None and e.eval_groups:
             if g.members[0] is n:
                 self._eval_siblings(g, Le)
@@ -515,7 +519,7 @@ class PlanBuilder:
             if n.bias or n.relu:
                 lst.add(_lib.OP_CONV_FWD_AFFINE, n.name, p=(self._a(n.x), self._wk(n), self._a(n.y), _vp(e.ones),
                            e._pptr(n.key + '.bias') if n.bias else _vp(e.zeros_k(n.K)), None),
-                        i=(0,), flags=4 if n.relu else 0, conv=d, lane=lane, reads=[ra(n.x)], writes=[ra(n.y)])
+                        i=(0,), flags=ops.FLAG_RELU if n.relu else 0, conv=d, lane=lane, reads=[ra(n.x)], writes=[ra(n.y)])
             else:
                 lst.add(_lib.OP_CONV_FWD, n.name, p=(self._a(n.x), self._wk(n), self._a(n.y), None), conv=d, lane=lane,
                         reads=[ra(n.x)], writes=[ra(n.y)])
@@ -531,7 +535,7 @@ class PlanBuilder:
 
     def _fwd_flat(self, k, n):
         for lst, lane in ((self.fwd_t, self.lane_of[n]), (self.fwd_e, self.lane_eval[n])):
-            lst.add(_lib.OP_FLATTEN_CHW, n.name, p=(self._a(n.x), self._a(n.y)), i=self._flat_i(n), flags=4, lane=lane,
+            lst.add(_lib.OP_FLATTEN_CHW, n.name, p=(self._a(n.x), self._a(n.y)), i=self._flat_i(n), flags=ops.FLAG_TO_CHW, lane=lane,
                     reads=[ra(n.x)], writes=[ra(n.y)])
 
     def _fwd_bnr(self, k, n):
@@ -628,7 +632,7 @@ class PlanBuilder:
         self.bwd.add(_lib.OP_BN_BWD, n.name, p=(self._a(n.x), self._a(n.y), self._a(n.y, True), e._pptr(bkey + '.weight'),
                         e._stat(n, 0), e._stat(n, 1), self._a(n.x, True), None, e._pptr(bkey + '.weight', 'G'),
                         e._pptr(bkey + '.bias', 'G'), e._stat(n, 2), e._stat(n, 3)),
-                     i=(n.K, n.x.buf.C, 0), flags=8 if acc else 0, bn=self._bnr_desc(n), lane=self.lane_of[n],
+                     i=(n.K, n.x.buf.C, 0), flags=ops.FLAG_DX_ACC if acc else 0, bn=self._bnr_desc(n), lane=self.lane_of[n],
                      reads=[ra(n.x), ra(n.y), rg(n.y), rst(n)], writes=[rg(n.x)])
 
     def _bwd_pool(self, k, n):
@@ -761,50 +765,43 @@ class PlanBuilder:
         annotation: loss ops are full barriers on lane 0, so their read-only operands need no resource entry"""
         e, N, NC = self.e, self.N, self.net.NC
         main = [h for h in e.heads if not h.aux][0]
-        # with class weights (TRAIN --class-norm): the same ops as OP_SOFTMAX_XENT_W, the weight tensor as a fifth operand
-        xent, cw = (_lib.OP_SOFTMAX_XENT, ()) if e.class_weight is None else (_lib.OP_SOFTMAX_XENT_W, (_vp(e.class_weight),))
-        # label smoothing (TRAIN --label-smoothing) is the second scalar of the same ops, either kind: f[1] != 0 sends the op to the
-        # smoothed kernel (ifcbk_softmax_xent_ls); without it f[1] stays the zero of a fresh op and the tables are what they were
-        ls = (e.label_smoothing,) if e.label_smoothing > 0 else ()
-        # the focusing exponent (TRAIN --focal-gamma) is the third scalar: f[2] != 0 sends the op to ifcbk_softmax_xent_focal; the
-        # engine refuses the two together, so f[1] is then the zero it writes here
-        if e.focal_gamma > 0:
-            ls = (0.0, e.focal_gamma)
-        # the factors of a mixed batch (TRAIN --mixup / --cutmix) are a sixth operand of the TRAIN loss ops: p[5] != NULL sends the op to
-        # ifcbk_softmax_xent_mix; the validation loss stays the one-target loss.  Without mix the tuples are what they were
-        mx = ((None,) * (1 - len(cw)) + (_vp(e.mix_lam[e.in_slot]),)) if e.mix else ()
-        # a teacher's logits (TRAIN --distill) are a seventh operand of the TRAIN loss ops, with alpha and the temperature as f[3], f[4]:
-        # p[6] != NULL sends the op to ifcbk_softmax_xent_distill; both heads of inception_v3 distil from the teacher's one set of logits,
-        # and the validation loss stays the hard loss.  Without distill the tuples are what they were
-        ds, dsf = (), ()
-        if e.distill is not None:
-            ds = (None,) * (2 - len(cw)) + (_vp(e.teacher_logits),)
-            dsf = (0.0,) * (2 - len(ls)) + e.distill
+        # an option adds its operands to the ops by name; which kernel a set of operands selects is the header's (IFCBK_OP_SOFTMAX_XENT)
+        xent, p, f = _lib.OP_SOFTMAX_XENT, dict(target=_vp(e.target), loss=_vp(e.loss)), {}
+        if e.class_weight is not None:                   # TRAIN --class-norm
+            xent, p['class_weight'] = _lib.OP_SOFTMAX_XENT_W, _vp(e.class_weight)
+        if e.label_smoothing > 0:                        # TRAIN --label-smoothing
+            f['smoothing'] = e.label_smoothing
+        if e.focal_gamma > 0:                            # TRAIN --focal-gamma (the engine refuses it together with smoothing)
+            f['gamma'] = e.focal_gamma
+        # the validation loss stays the one-target hard loss; both heads of inception_v3 distil from the teacher's one set of logits
+        tp, tf = dict(p), dict(f)
+        if e.mix:                                        # TRAIN --mixup / --cutmix
+            tp['lam'] = _vp(e.mix_lam[e.in_slot])
+        if e.distill is not None:                        # TRAIN --distill
+            tp['teacher'] = _vp(e.teacher_logits)
+            tf['alpha'], tf['temperature'] = e.distill
         lossl, evl = OpList(), OpList()
         for h in [main] + [h for h in e.heads if h.aux]:
-            lossl.add(xent, 'loss_aux' if h.aux else 'loss', p=(_vp(h.logits), _vp(e.target), _vp(e.loss), _vp(h.dlogits)) + cw + mx + ds,
-                      i=(N, NC), f=((0.4,) if h.aux else (1.0,)) + ls + dsf, flags=1 if h.aux else 0)
-        evl.add(xent, 'val_loss', p=(_vp(main.logits), _vp(e.target), _vp(e.loss), None) + cw, i=(N, NC), f=(1.0,) + ls)
+            lossl.add(xent, 'loss_aux' if h.aux else 'loss', p=dict(tp, logits=_vp(h.logits), dlogits=_vp(h.dlogits)), i=(N, NC),
+                      f=dict(tf, weight=0.4 if h.aux else 1.0), flags=ops.FLAG_ACC if h.aux else 0)
+        evl.add(xent, 'val_loss', p=dict(p, logits=_vp(main.logits)), i=(N, NC), f=dict(f, weight=1.0))
         return lossl, evl, main
 
     def _optimizer_op(self):
         e, opt = self.e, OpList()
-        # the weight average (TRAIN --ema) is one more operand of the optimizer op, behind those of the plain step: E at the offset of P
-        # (every bucket's op carries its slice); its weight is stamped per step (_set_update).  Without it the tuples are what they were
-        ema = (_vp(e.E),) if e.ema_decay is not None else ()
-        # the clip state (TRAIN --clip-grad) is the operand behind the average, with max_norm as the scalar behind the average's weight:
-        # the op then takes the norm of the whole of G (ifcbk_grad_norm) ahead of its update.  Without it the tuples are what they were
-        clip, clipf = (), ()
-        if e.clip_grad is not None:
-            clip = (None,) * (1 - len(ema)) + (_vp(e.clip_state),)
-            clipf = (0.0, e.clip_grad)
+        # step, grad_scale and ema_w are stamped per step (Engine._set_update)
+        p, f = dict(P=_vp(e.P), G=_vp(e.G)), dict(lr=e.lr, weight_decay=e.weight_decay, grad_scale=1.0)
+        if e.ema_decay is not None:                      # TRAIN --ema: E at the offset of P (every bucket's op carries its slice)
+            p['E'] = _vp(e.E)
+        if e.clip_grad is not None:                      # TRAIN --clip-grad: the op takes the norm of the whole of G ahead of its update
+            p['clip_state'], f['max_norm'] = _vp(e.clip_state), e.clip_grad
         if e.optimizer == 'sgd':
             # additive option (north_star "SGD/Adam step"; upstream only has Adam): torch.optim.SGD's update, momentum buffer = M
-            opt.add(_lib.OP_SGD, 'sgd', p=(_vp(e.P), _vp(e.G), _vp(e.M) if e.momentum else None) + ema + clip,
-                    i=(e.nparam_padded, 1), f=(e.lr, e.momentum, e.weight_decay, 1.0) + clipf)
+            opt.add(_lib.OP_SGD, 'sgd', p=dict(p, M=_vp(e.M) if e.momentum else None), i=dict(n=e.nparam_padded, step=1),
+                    f=dict(f, momentum=e.momentum))
         else:
-            opt.add(_lib.OP_ADAM, 'adam', p=(_vp(e.P), _vp(e.G), _vp(e.M), _vp(e.V)) + ema + clip,
-                    i=(e.nparam_padded, 1), f=(e.lr, e.betas[0], e.betas[1], e.eps, e.weight_decay, 1.0) + clipf)
+            opt.add(_lib.OP_ADAM, 'adam', p=dict(p, M=_vp(e.M), V=_vp(e.V)), i=dict(n=e.nparam_padded, step=1),
+                    f=dict(f, beta1=e.betas[0], beta2=e.betas[1], eps=e.eps))
         return opt
 
     def _assemble(self):
@@ -837,17 +834,19 @@ class PlanBuilder:
         return pl
 
     def _bucket_opt(self, lst, opt, lo, hi, **sched):
-        """the optimizer op over [lo, hi) of the flat buffers: the pointers of the whole-buffer op (P, G, M (, V) (, E)) moved to the slice"""
-        e, o0 = self.e, opt.ops[0]
-        nptr = (4 if e.optimizer != 'sgd' else 3) + (1 if e.ema_decay is not None else 0)
-        lst.add(o0.kind, opt.tags[0] + '[%d:%d]' % (lo, hi), p=[(o0.p[j] + 4 * lo) if o0.p[j] else None for j in range(nptr)],
-                i=(hi - lo, int(o0.i[1])), f=tuple(o0.f[j] for j in range(8)), **sched)
+        """the optimizer op over [lo, hi) of the flat buffers: the whole-buffer op with its slices of them (P, G, M, V, E) moved to lo and
+        n = hi - lo.  Any other pointer (the clip state: a clipped plan takes the single update) has no per-bucket form"""
+        o0 = opt.ops[0]
+        row = ops.OPERANDS[o0.kind]
+        p = {name: v + 4 * lo for name, v in zip(row['p'], o0.p) if v}
+        assert set(p) <= set('PGMVE'), 'optimizer op with a pointer that is no slice of a flat buffer: %s' % sorted(set(p) - set('PGMVE'))
+        lst.add(o0.kind, opt.tags[0] + '[%d:%d]' % (lo, hi), p=p, i=dict(zip(row['i'], o0.i), n=hi - lo), f=dict(zip(row['f'], o0.f)), **sched)
 
     def _packs_in(self, pack_ops, lo, hi):
         """the multi-tensor repack of the pack ops whose fp32 master lies in [lo, hi) of the flat buffer (an empty list: none does)"""
         pbase, sub = self.e.P.data_ptr(), OpList()
         for o, tg, mt in zip(pack_ops.ops, pack_ops.tags, pack_ops.meta):
-            if lo <= (o.p[0] - pbase) // 4 < hi:
+            if lo <= (o.p[_PACK_MASTER] - pbase) // 4 < hi:
                 sub.ops.append(o); sub.tags.append(tg); sub.meta.append(mt)
         return self.e._pack_multi(sub, key=(lo, hi)) if sub.ops else OpList()
 
@@ -860,12 +859,12 @@ class PlanBuilder:
         skey = lambda off: next((r0 for r0, r1 in regions if r0 <= off < r1), off)
         owners = {}
         for o in pack_ops.ops:
-            if o.p[2]:
-                owners.setdefault(skey((o.p[2] - sbase) // e.esize), []).append((o.p[0] - pbase) // 4)
+            if o.p[_PACK_WT]:
+                owners.setdefault(skey((o.p[_PACK_WT] - sbase) // e.esize), []).append((o.p[_PACK_MASTER] - pbase) // 4)
         last_reader, shreads = {}, {}
         for k, o in enumerate(bwd.ops):
-            if o.kind in (_lib.OP_CONV_DGRAD, _lib.OP_CONV_DGRAD_BNSTAT):
-                own = owners.get(skey((o.p[1] - sbase) // e.esize))
+            if o.kind in _DGRAD_WT:
+                own = owners.get(skey((o.p[_DGRAD_WT[o.kind]] - sbase) // e.esize))
                 if own is None:
                     return None
                 shreads[k] = [('SH', off, off + e.palloc[off]) for off in own]

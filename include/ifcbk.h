@@ -541,17 +541,50 @@ enum {
     IFCBK_OP_CONV_FWD = 1, IFCBK_OP_CONV_DGRAD, IFCBK_OP_CONV_WGRAD, IFCBK_OP_WEIGHT_PACK,
     IFCBK_OP_BN_FINALIZE, IFCBK_OP_BN_APPLY, IFCBK_OP_BN_BWD,
     IFCBK_OP_MAXPOOL_FWD, IFCBK_OP_MAXPOOL_BWD, IFCBK_OP_AVGPOOL_FWD, IFCBK_OP_AVGPOOL_BWD,
-    IFCBK_OP_HEAD_FWD, IFCBK_OP_HEAD_BWD, IFCBK_OP_SOFTMAX_XENT, IFCBK_OP_SOFTMAX,
-    IFCBK_OP_ADAM, IFCBK_OP_MEMSET, IFCBK_OP_COPY2D, IFCBK_OP_DROPOUT_MASK, IFCBK_OP_CONV_FWD_AFFINE,
+    IFCBK_OP_HEAD_FWD, IFCBK_OP_HEAD_BWD,
+    /* IFCBK_OP_SOFTMAX_XENT and IFCBK_OP_SOFTMAX_XENT_W (the last kind of this list), one layout.  flags bit 0: accumulate into loss.
+     * A NULL pointer or a zero scalar, what a zeroed op holds, is the option switched off.
+     *   slot = what it holds                                                                    [name, where it is not the first word]
+     *   p[0] = logits, float[N][NC]
+     *   p[1] = target, int64[N]
+     *   p[2] = loss, float[1]
+     *   p[3] = dlogits, float[N][NC]; nullable: the loss alone
+     *   p[4] = class_weight, float[NC]; read by the _W kind only (without an option below it refuses NULL: ifcbk_softmax_xent_w)
+     *   p[5] = the factors of a mixed batch, float[N]: ifcbk_softmax_xent_mix                     [lam]
+     *   p[6] = a teacher's logits, float[N][NC]: ifcbk_softmax_xent_distill                       [teacher]
+     *   i[0] = N, i[1] = NC
+     *   f[0] = weight of this loss in the sum
+     *   f[1] = label smoothing factor: ifcbk_softmax_xent_ls; the label_smoothing of the mix and distill calls  [smoothing]
+     *   f[2] = focal-loss gamma: ifcbk_softmax_xent_focal                                         [gamma]
+     *   f[3] = alpha, f[4] = temperature of the distill call
+     * Every call takes p[0..3], i, f[0] and class_weight (NULL for the plain kind).  Dispatch: teacher, else lam, else smoothing, else
+     * gamma, else ifcbk_softmax_xent / ifcbk_softmax_xent_w.  IFCBK_EINVAL, checked in this order: f[1] != 0 together with f[2] != 0;
+     * teacher together with f[2] != 0; teacher together with lam; lam together with f[2] != 0. */
+    IFCBK_OP_SOFTMAX_XENT,
+    IFCBK_OP_SOFTMAX,
+    /* IFCBK_OP_ADAM: ifcbk_adam_clip_flat.  A NULL E or clip_state, what a zeroed op holds, is the step without it.
+     *   p[0] = P, p[1] = G, p[2] = M, p[3] = V: the flat fp32 buffers, or one op's slice of each
+     *   p[4] = E, the weight average's slice (nullable)
+     *   p[5] = clip_state (nullable): the op then takes the norm of its G first (ifcbk_grad_norm)
+     *   i[0] = n, i[1] = step
+     *   f[0] = lr, f[1] = beta1, f[2] = beta2, f[3] = eps, f[4] = weight_decay, f[5] = grad_scale
+     *   f[6] = ema_w, read with E
+     *   f[7] = max_norm, read with clip_state */
+    IFCBK_OP_ADAM,
+    IFCBK_OP_MEMSET, IFCBK_OP_COPY2D, IFCBK_OP_DROPOUT_MASK, IFCBK_OP_CONV_FWD_AFFINE,
     IFCBK_OP_WEIGHT_PACK_MULTI, IFCBK_OP_CONV_WGRAD_SEG, IFCBK_OP_BN_APPLY_MAXPOOL, IFCBK_OP_BN_BWD_MAXPOOL,
     IFCBK_OP_CONV_DGRAD_BNSTAT, IFCBK_OP_BN_BWD_PARTIALS, IFCBK_OP_BN_STATS, IFCBK_OP_AVGPOOL_AFFINE,
     IFCBK_OP_CONV_FWD_AFFINE_SEG,
-    IFCBK_OP_SGD,            /* p: P, G, momentum buffer (nullable); i[0] = n; f: lr, momentum, weight decay, grad scale.
-                              * p[3] = the weight average's slice (nullable), f[4] = ema_w: ifcbk_sgd_ema_flat.  IFCBK_OP_ADAM (p: P, G, M,
-                              * V; i: n, step; f: lr, beta1, beta2, eps, weight decay, grad scale) takes them as p[4] and f[6]:
-                              * ifcbk_adam_ema_flat.  NULL, what a zeroed op holds, is the step without an average.
-                              * p[4] = the clip state (nullable), f[5] = max_norm: ifcbk_sgd_clip_flat; IFCBK_OP_ADAM takes them as p[5] and
-                              * f[7]: ifcbk_adam_clip_flat.  NULL, what a zeroed op holds, is the step without clipping              */
+    /* IFCBK_OP_SGD: ifcbk_sgd_clip_flat.  A NULL M, E or clip_state, what a zeroed op holds, is the step without it.
+     *   p[0] = P, p[1] = G: the flat fp32 buffers, or one op's slice of each
+     *   p[2] = M, the momentum buffer (nullable)
+     *   p[3] = E, the weight average's slice (nullable)
+     *   p[4] = clip_state (nullable): the op then takes the norm of its G first (ifcbk_grad_norm)
+     *   i[0] = n (i[1], IFCBK_OP_ADAM's step, is not read)
+     *   f[0] = lr, f[1] = momentum, f[2] = weight_decay, f[3] = grad_scale
+     *   f[4] = ema_w, read with E
+     *   f[5] = max_norm, read with clip_state */
+    IFCBK_OP_SGD,
     IFCBK_OP_RETIRED_31,     /* retired (was the per-chunk-table dgrad + BatchNorm-backward sums); the slot keeps the numbering */
     IFCBK_OP_BIAS_RELU_BWD,  /* p: y, dy, dz, dbias; u.bn: M, C, ldx = ld(y), ldy = ld(dy), relu, dtype; i[0] = ld(dz)          */
     IFCBK_OP_DROPOUT,        /* p: x, mask (nullable), y; i[0] = n, i[1] = dtype; f[0] = scale; flags bit 0 accumulate           */
@@ -562,19 +595,7 @@ enum {
     IFCBK_OP_STEP_COUNTERS,  /* p: num_batches_tracked (i64, nullable), loss_sum (nullable), loss; i[0] = number of BatchNorms      */
     IFCBK_OP_CONV_WGRAD_GROUP,/* p[0]: HOST array of i[0] ifcbk_wgrad_item entries, kept alive by the caller; p[1..]: the members' dw again
                                * (what the data-parallel bucket planner reads); flags bit 0 accumulate                            */
-    IFCBK_OP_SOFTMAX_XENT_W  /* p: logits, target, loss, dlogits (nullable), class_weight; i: N, NC; f[0] = weight; flags bit 0 accumulate.
-                              * f[1] = label smoothing factor, for this kind and for IFCBK_OP_SOFTMAX_XENT (p: logits, target, loss, dlogits
-                              * (nullable); i: N, NC; f[0] = weight): 0, what a zeroed op holds, is the unsmoothed call; any other value
-                              * runs ifcbk_softmax_xent_ls with the same operands (class_weight = p[4] here, NULL for the plain kind).
-                              * f[2] = focal-loss gamma, for the same two kinds: 0 is today's call; any other value runs
-                              * ifcbk_softmax_xent_focal with the same operands; f[1] != 0 together with f[2] != 0 is IFCBK_EINVAL.
-                              * p[5] = the factors of a mixed batch (float[N], device), for the same two kinds: NULL, what a zeroed op
-                              * holds, is the dispatch above; an array runs ifcbk_softmax_xent_mix with the same operands and f[1] as its
-                              * label smoothing; an array together with f[2] != 0 is IFCBK_EINVAL.
-                              * p[6] = a teacher's logits (float[N][NC], device), f[3] = alpha, f[4] = temperature, for the same two kinds:
-                              * NULL, what a zeroed op holds, is the dispatch above; an array runs ifcbk_softmax_xent_distill with the
-                              * same operands, f[1] as its label smoothing and p[4] as its class weights (NULL for the plain kind); an
-                              * array together with f[2] != 0 or with p[5] is IFCBK_EINVAL                                              */
+    IFCBK_OP_SOFTMAX_XENT_W  /* the layout block at IFCBK_OP_SOFTMAX_XENT; this kind reads p[4], the class weights */
 };
 typedef struct {
     ifcbk_conv_desc d;

@@ -27,6 +27,8 @@ GOLDEN = os.path.join(HERE, 'plan_fingerprints.json')
 PROGRAMS = ('fwd_train', 'fwd_eval', 'bwd', 'pack', 'evalprep', 'loss', 'eval_loss', 'softmax', 'adam', 'step', 'fwd_loss',
             'fwd_bwd', 'adam_pack')
 
+_CW = [1.0, 0.5, 2.0, 1.5, 0.25, 3.0, 1.0]
+
 # name -> (model, dtype, batch, extra Engine kwargs, environment)
 CONFIGS = {
     'inception_v3-bf16-b2': ('inception_v3', 'bf16', 2, {}, {}),
@@ -56,6 +58,17 @@ CONFIGS = {
     'inception_v3-bf16-b2-distill': ('inception_v3', 'bf16', 2, {'distill': (0.5, 2.0)}, {}),
     'inception_v3-bf16-b2-fuse_pool_eval0': ('inception_v3', 'bf16', 2, {}, {'IFCBK_FUSE_POOL_EVAL': '0'}),
     'inception_v3-bf16-b2-fuse_siblings0': ('inception_v3', 'bf16', 2, {}, {'IFCBK_FUSE_SIBLINGS': '0'}),
+    # optional operands of the loss and optimizer ops, alone and together (a clipped plan takes the single update)
+    'inception_v3-bf16-b2-clip': ('inception_v3', 'bf16', 2, {'clip_grad': 1.0}, {}),
+    'inception_v3-bf16-b2-ema-clip': ('inception_v3', 'bf16', 2, {'ema_decay': 0.999, 'clip_grad': 1.0}, {}),
+    'inception_v3-bf16-b2-sgd-ema-clip': ('inception_v3', 'bf16', 2, {'optimizer': 'sgd', 'momentum': 0.9, 'ema_decay': 0.999,
+                                                                      'clip_grad': 1.0}, {}),
+    'inception_v3-bf16-b2-sgd0-clip': ('inception_v3', 'bf16', 2, {'optimizer': 'sgd', 'momentum': 0.0, 'clip_grad': 1.0}, {}),
+    'inception_v3-bf16-b2-class_weights-ls-mix': ('inception_v3', 'bf16', 2, {'class_weights': _CW, 'label_smoothing': 0.1,
+                                                                              'mix': True}, {}),
+    'inception_v3-bf16-b2-class_weights-ls-distill': ('inception_v3', 'bf16', 2, {'class_weights': _CW, 'label_smoothing': 0.1,
+                                                                                  'distill': (0.5, 2.0)}, {}),
+    'inception_v3-bf16-b2-ema-dp2': ('inception_v3', 'bf16', 2, {'ema_decay': 0.999, 'dp_world': 2}, {}),
 }
 
 # configurations planned on the resized u8 plane of the input slot (eng.in_kind) instead of the dense tensor

@@ -221,9 +221,15 @@ def test_the_old_entry_points_are_this_call():
     assert src.count('hipLaunchKernelGGL(adam_kernel') == 1 and src.count('hipLaunchKernelGGL(sgd_kernel') == 1
     # run_one hands the operands over: p[5] / f[7] of IFCBK_OP_ADAM, p[4] / f[5] of IFCBK_OP_SGD
     ctx = open(os.path.join(ROOT, 'ifcb_classifier_amd', 'csrc', 'ctx.hip')).read()
-    assert 'o->p[o->kind == IFCBK_OP_ADAM ? 5 : 4]' in ctx
-    assert re.search(r'ifcbk_adam_clip_flat\(c,[^;]*op_ema\(o\),[^;]*o->f\[5\], o->f\[6\], o->f\[7\], op_clip\(o\), st\);', ctx)
-    assert re.search(r'ifcbk_sgd_clip_flat\(c,[^;]*op_ema\(o\),[^;]*o->f\[3\], o->f\[4\], o->f\[5\], op_clip\(o\), st\);', ctx)
+    # (by the slot names ctx.hip declares: the first enumerator of a row is slot 0)
+    assert re.search(r'enum \{\s*// IFCBK_OP_ADAM\n\s*ADAM_P, ADAM_G, ADAM_M, ADAM_V, ADAM_E, ADAM_CLIP_STATE,', ctx)
+    assert re.search(r'\n\s*ADAM_LR = 0, ADAM_BETA1, ADAM_BETA2, ADAM_EPS, ADAM_WEIGHT_DECAY, ADAM_GRAD_SCALE, ADAM_EMA_W, ADAM_MAX_NORM\s', ctx)
+    assert re.search(r'enum \{\s*// IFCBK_OP_SGD\n\s*SGD_P, SGD_G, SGD_M, SGD_E, SGD_CLIP_STATE,', ctx)
+    assert re.search(r'\n\s*SGD_LR = 0, SGD_MOMENTUM, SGD_WEIGHT_DECAY, SGD_GRAD_SCALE, SGD_EMA_W, SGD_MAX_NORM\s', ctx)
+    assert re.search(r'ifcbk_adam_clip_flat\(c,[^;]*\(float\*\)p\[ADAM_E\],[^;]*o->f\[ADAM_GRAD_SCALE\], o->f\[ADAM_EMA_W\], o->f\[ADAM_MAX_NORM\],\s*'
+                     r'\(float\*\)p\[ADAM_CLIP_STATE\], st\);', ctx)
+    assert re.search(r'ifcbk_sgd_clip_flat\(c,[^;]*\(float\*\)p\[SGD_E\],[^;]*o->f\[SGD_GRAD_SCALE\], o->f\[SGD_EMA_W\], o->f\[SGD_MAX_NORM\],\s*'
+                     r'\(float\*\)p\[SGD_CLIP_STATE\], st\);', ctx)
 
 
 # ------------------------------------------------------------------------------------------------------ the reference and the bound

@@ -195,9 +195,14 @@ def test_the_new_operand_is_not_const_in_the_typed_entry_points():
     assert len(_lib._PROTOS['ifcbk_ema_flat'][1]) == len(protos['ifcbk_ema_flat'])
     # run_one hands the operand over: p[4] / f[6] of IFCBK_OP_ADAM, p[3] / f[4] of IFCBK_OP_SGD
     src = open(os.path.join(ROOT, 'ifcb_classifier_amd', 'csrc', 'ctx.hip')).read()
-    assert 'o->p[o->kind == IFCBK_OP_ADAM ? 4 : 3]' in src
-    assert re.search(r'ifcbk_adam_ema_flat\(c,[^;]*op_ema\(o\),[^;]*o->f\[5\], o->f\[6\], st\);', src)
-    assert re.search(r'ifcbk_sgd_ema_flat\(c,[^;]*op_ema\(o\),[^;]*o->f\[3\],\s*o->f\[4\], st\);', src)
+    # (by the slot names ctx.hip declares, the first enumerator of a row being slot 0; through the clipping entry point, which a NULL
+    # clip state makes the _ema_flat call)
+    assert re.search(r'enum \{\s*// IFCBK_OP_ADAM\n\s*ADAM_P, ADAM_G, ADAM_M, ADAM_V, ADAM_E,', src)
+    assert re.search(r'\n\s*ADAM_LR = 0, ADAM_BETA1, ADAM_BETA2, ADAM_EPS, ADAM_WEIGHT_DECAY, ADAM_GRAD_SCALE, ADAM_EMA_W,', src)
+    assert re.search(r'enum \{\s*// IFCBK_OP_SGD\n\s*SGD_P, SGD_G, SGD_M, SGD_E,', src)
+    assert re.search(r'\n\s*SGD_LR = 0, SGD_MOMENTUM, SGD_WEIGHT_DECAY, SGD_GRAD_SCALE, SGD_EMA_W,', src)
+    assert re.search(r'ifcbk_adam_clip_flat\(c,[^;]*\(float\*\)p\[ADAM_E\],[^;]*o->f\[ADAM_GRAD_SCALE\], o->f\[ADAM_EMA_W\],', src)
+    assert re.search(r'ifcbk_sgd_clip_flat\(c,[^;]*\(float\*\)p\[SGD_E\],[^;]*o->f\[SGD_GRAD_SCALE\], o->f\[SGD_EMA_W\],', src)
 
 
 @pytest.mark.parametrize('model,optimizer,momentum', CASES)
