@@ -169,6 +169,7 @@ _PROTOS = {
     'ifcbk_roi_jitter_workspace': (_sz, [_i]),
     'ifcbk_roi_gather': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, C.c_int64, _vp, _vp, _vp, _vp]),
     'ifcbk_batch_mix': (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, _vp]),
+    'ifcbk_batch_blur': (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp]),
     'ifcbk_batch_sym': (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     'ifcbk_u8_channel_moments': (_i, [_vp, _vp, _i, C.c_int64, _i, _vp, _vp]),
     'ifcbk_stem_u8_rows': (_i, [C.POINTER(ConvDesc)]),

@@ -91,7 +91,8 @@ class Engine:
 
     def __init__(self, net, device=0, max_batch=32, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, dtype='bf16', optimizer='adam',
                  momentum=0.0, plan_only=False, train_batch=None, dp_world=None, class_weights=None, weight_decay=0.0,
-                 label_smoothing=0.0, focal_gamma=0.0, mix=False, ema_decay=None, ema_warmup=True, distill=None, clip_grad=None):
+                 label_smoothing=0.0, focal_gamma=0.0, mix=False, ema_decay=None, ema_warmup=True, distill=None, clip_grad=None,
+                 blur_radius=None):
         # dp_world: world size of the data-parallel job this replica belongs to (None: WORLD_SIZE of the launcher, else an
         # initialised torch.distributed group, else 1) -- it picks the program-lane default, and train_step_ddp checks it
         self._dp_world_arg = None if dp_world is None else int(dp_world)
@@ -131,6 +132,13 @@ class Engine:
         # additive (TRAIN --mixup / --cutmix): the train loss ops read per-image mix factors from a device array (mix_lam) and run the
         # two-target kernel; mix_batch() mixes a loaded batch with its reverse.  False: buffers, plans and launches are what they were
         self.mix = bool(mix)
+        # additive (TRAIN --blur): the radius of the run's Gaussian window, 1..12; load_rois(blur=sigmas) then blurs the resized batch in
+        # place (ifcbk_batch_blur).  None: load_rois refuses sigmas.  No buffer, plan or op depends on it
+        self.blur_radius = None if blur_radius is None else int(blur_radius)
+        if self.blur_radius is not None and not (1 <= self.blur_radius <= 12 and self.blur_radius == blur_radius):
+            raise ValueError('blur_radius must be an integer 1..12, or None for an engine that never blurs')
+        if self.blur_radius is not None and self.blur_radius >= net.S:
+            raise ValueError('blur_radius %d >= the input side %d: the reflected border needs r < S' % (self.blur_radius, net.S))
         if self.mix and self.focal_gamma > 0:
             raise ValueError('mix and focal_gamma do not combine: give one of them')
         # additive (TRAIN --distill): (alpha, T) -- the train loss ops run Hinton's loss (ifcbk_softmax_xent_distill) against the logits in
@@ -988,7 +996,7 @@ class Engine:
         return N
 
     def load_rois(self, pixels, offs, hs, ws, max_h, max_w, in_channels=1, flips=None, mean=None, std=None, slot=None, turn=False, pad=None,
-                  jitter=None):
+                  jitter=None, blur=None):
         """ragged u8 ROIs (device tensors) -> input buffer via the PIL-exact resize kernel.  slot: the input slot of a
         prefetch (runs on the prefetch stream with the prefetch context's workspace); None = the current slot, current stream.
         turn: the codes in ``flips`` may hold bit 2 = transpose (TRAIN --rot90; neuston_data.fold_turns).
@@ -996,12 +1004,31 @@ class Engine:
         (TRAIN --pad; ifcbk_roi_preprocess_fit).
         jitter: None, or (brightness, contrast): float32 device tensors of one factor per ROI, either may be None (TRAIN --jitter).
         ifcbk_roi_jitter then maps the ROIs IN PLACE ahead of the resize, on the same ctx and stream: ``pixels`` is overwritten
-        with the jittered ROIs."""
+        with the jittered ROIs.
+        blur: None, or a float32 device tensor of one sigma per ROI, 0 = leave the image alone (TRAIN --blur).  ifcbk_batch_blur then
+        blurs the RESIZED batch in place with the engine's ``blur_radius``, behind the resize on the same ctx and stream, on whichever
+        buffer the resize wrote (the u8 plane or the dense tensor), so plans and captured graphs keep their addresses; a ``mix_batch``
+        of the slot comes after it.  Without ``blur`` nothing more is launched."""
+        if blur is not None:
+            n = hs.numel()
+            if self.blur_radius is None:
+                raise RuntimeError('load_rois(blur=): this engine was built without blur_radius')
+            if not (torch.is_tensor(blur) and blur.dtype == torch.float32 and blur.device == pixels.device and blur.numel() == n
+                    and blur.is_contiguous()):
+                raise ValueError('blur: a float32 tensor of %d sigmas on %s, or None' % (n, pixels.device))
         if slot is not None:
-            return self._load_rois_into(self.pre_ctx, C.c_void_p(self.pre_stream.cuda_stream), slot, False,
-                                        pixels, offs, hs, ws, max_h, max_w, in_channels, flips, mean, std, turn, pad, jitter)
-        return self._load_rois_into(self.ctx, self.stream(), self.in_slot, True, pixels, offs, hs, ws, max_h,
-                                    max_w, in_channels, flips, mean, std, turn, pad, jitter)
+            ctx, stream, s = self.pre_ctx, C.c_void_p(self.pre_stream.cuda_stream), slot
+            n = self._load_rois_into(ctx, stream, s, False, pixels, offs, hs, ws, max_h, max_w, in_channels, flips, mean, std, turn, pad, jitter)
+        else:
+            ctx, stream, s = self.ctx, self.stream(), self.in_slot
+            n = self._load_rois_into(ctx, stream, s, True, pixels, offs, hs, ws, max_h, max_w, in_channels, flips, mean, std, turn, pad, jitter)
+        if blur is not None:
+            if self.in_kind[s] == 'u8':
+                buf, kind = self.in_u8[s], _lib.MIX_U8
+            else:
+                buf, kind = self.in_bufs[s], self.cdtype
+            ctx.call('ifcbk_batch_blur', _vp(buf), kind, n, self.net.S, _vp(blur), self.blur_radius, stream)
+        return n
 
     def _load_rois_into(self, ctx, stream, slot, main, pixels, offs, hs, ws, max_h, max_w, in_channels, flips, mean, std, turn=False, pad=None,
                         jitter=None):

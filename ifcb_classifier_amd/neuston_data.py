@@ -13,6 +13,7 @@ import random
 
 import numpy as np
 import torch
+from torch.utils.data import get_worker_info
 from torch.utils.data.dataset import Dataset
 
 # torchvision.datasets.folder.IMG_EXTENSIONS (the reference filters files with it, neuston_data.py:69)
@@ -33,8 +34,12 @@ def default_loader(path):
 class RoiTransform:
     """What ``transforms.Compose([flips] + [Resize, ToTensor, Normalize?])`` means on the GPU path."""
 
-    def __init__(self, resize, img_norm=None, vflip=False, hflip=False, rot90=False, pad=None, jitter=None, mix=None):
+    def __init__(self, resize, img_norm=None, vflip=False, hflip=False, rot90=False, pad=None, jitter=None, mix=None, blur=None, blur_prob=None,
+                 seed=0, rank=0):
         self.resize = resize
+        # --blur / --blur-prob: None, or SIGMA_MAX of the Gaussian defocus and the probability that an image is blurred at all
+        self.blur, self.blur_prob = parse_blur(blur), parse_blur_prob(blur_prob)
+        self._blur_seed, self._blur_rng, self._blur_worker = (int(seed or 0) & 0xffffffffffffffff, int(rank)), None, None
         self.mix = mix                    # --mixup / --cutmix: None, or the BatchMix that draws per batch (the training transform only)
         self.jitter = parse_jitter(jitter)   # --jitter: None, or [B, C] = the brightness / contrast ranges of ColorJitter (not both 0)
         self.pad = parse_pad(pad)         # --pad: None = squash to resize x resize, 'border' / 0..255 = keep the aspect ratio, fill the rest
@@ -62,6 +67,79 @@ class RoiTransform:
         if self.jitter is None:
             return None, None
         return tuple(float(np.float32(random.uniform(max(0.0, 1.0 - r), 1.0 + r))) if r > 0 else None for r in self.jitter)
+
+    def blur_sigma(self):
+        """the sigma of this item's Gaussian blur, a float32 value: uniform in [0.1, SIGMA_MAX] (torchvision's ``GaussianBlur(k,
+        sigma=(0.1, SIGMA_MAX))``) with probability ``blur_prob``, else 0.0 = not blurred.  Two numbers per item -- blurred at all, then
+        sigma -- whatever the first says, from a generator of this object's own, seeded from (seed, rank): neither ``random`` nor the
+        global numpy / torch streams are touched, so no flip, turn or jitter draw moves.  In a DataLoader worker the generator is seeded
+        from the worker's seed as well, once per worker: the forked copies of one state would repeat each other's draws."""
+        if self.blur is None:
+            return 0.0
+        info = get_worker_info()
+        if self._blur_rng is None or (info is not None and self._blur_worker != (info.id, info.seed)):
+            key = [0x626c7572, self._blur_seed[0], self._blur_seed[1]]
+            if info is not None:
+                key.append(int(info.seed) & 0xffffffffffffffff)
+                self._blur_worker = (info.id, info.seed)
+            self._blur_rng = np.random.Generator(np.random.PCG64(np.random.SeedSequence(key)))
+        u, v = self._blur_rng.random(2)
+        if not u < self.blur_prob:
+            return 0.0
+        return float(np.float32(BLUR_SIGMA_MIN + v * (self.blur - BLUR_SIGMA_MIN)))
+
+
+BLUR_SIGMA_MIN = 0.1          # torchvision's default low end of GaussianBlur's sigma range
+BLUR_SIGMA_LIMIT = 4.0        # the largest SIGMA_MAX: radius ceil(3 * 4) = 12, the kernel's largest window
+
+
+def parse_blur(value):
+    """``--blur SIGMA_MAX`` / a checkpoint's ``blur``: None (unset) or a finite float in (0.1, 4]"""
+    if value is None:
+        return None
+    if isinstance(value, bool):
+        raise ValueError('blur: SIGMA_MAX expected, got %r' % (value,))
+    v = float(value)                                                    # (float('a') raises ValueError too)
+    if not BLUR_SIGMA_MIN < v <= BLUR_SIGMA_LIMIT:                      # (nan fails both comparisons)
+        raise ValueError('blur: SIGMA_MAX must be a float in (0.1, 4], got %r' % (value,))
+    return v
+
+
+def parse_blur_prob(value):
+    """``--blur-prob P`` / a checkpoint's ``blur_prob``: None -> 0.5, else a float in [0, 1]"""
+    if value is None:
+        return 0.5
+    if isinstance(value, bool):
+        raise ValueError('blur-prob: P expected, got %r' % (value,))
+    v = float(value)
+    if not 0.0 <= v <= 1.0:                                             # (nan fails both comparisons)
+        raise ValueError('blur-prob: P must be in [0, 1], got %r' % (value,))
+    return v
+
+
+def blur_radius(sigma_max):
+    """the window of a run with ``--blur SIGMA_MAX``: radius r = ceil(3 SIGMA_MAX) (kernel_size 2 r + 1), 1..12; None -> None"""
+    import math
+    sigma_max = parse_blur(sigma_max)
+    return None if sigma_max is None else int(math.ceil(3.0 * sigma_max))
+
+
+def blur_arg(text):
+    """argparse ``type=`` of ``--blur SIGMA_MAX`` (neuston_net TRAIN)"""
+    import argparse
+    try:
+        return parse_blur(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError('SIGMA_MAX must be a float in (0.1, 4], got %r' % text)
+
+
+def blur_prob_arg(text):
+    """argparse ``type=`` of ``--blur-prob P`` (neuston_net TRAIN)"""
+    import argparse
+    try:
+        return parse_blur_prob(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError('P must be a float in [0, 1], got %r' % text)
 
 
 def parse_jitter(value):
@@ -476,6 +554,11 @@ class NeustonDataset(Dataset):
         path = self.images[index]
         data = default_loader(path)
         flip = self.transforms.flip_code() if self.transforms is not None else 0
+        if self.transforms is not None and getattr(self.transforms, 'blur', None) is not None:
+            # (field six: the sigma of this draw's Gaussian blur, 0.0 = none; fields four and five as below, None without jitter)
+            tr = self.transforms
+            fbc = tr.jitter_factors() if getattr(tr, 'jitter', None) is not None else (None, None)
+            return (data, flip, bool(getattr(tr, 'rot90', False))) + fbc + (tr.blur_sigma(),), self.targets[index], path
         if self.transforms is not None and getattr(self.transforms, 'jitter', None) is not None:
             # (fields four and five: the brightness and contrast factors of this draw, None for a zero range)
             return (data, flip, bool(getattr(self.transforms, 'rot90', False))) + self.transforms.jitter_factors(), self.targets[index], path
@@ -546,7 +629,10 @@ def get_trainval_transforms(args):
     if mixup > 0 or cutmix > 0:
         mix = BatchMix(mixup, cutmix, parse_mix_prob(getattr(args, 'mix_prob', None)), seed=getattr(args, 'seed', 0) or 0,
                        rank=int(os.environ.get('RANK', 0)))
-    train = RoiTransform(args.resize, norm, vflip, hflip, rot90=bool(rot90), pad=pad, jitter=jitter, mix=mix)
+    # Gaussian defocus (--blur / --blur-prob): the training set only; its draws have a generator of their own
+    train = RoiTransform(args.resize, norm, vflip, hflip, rot90=bool(rot90), pad=pad, jitter=jitter, mix=mix,
+                         blur=getattr(args, 'blur', None), blur_prob=getattr(args, 'blur_prob', None),
+                         seed=getattr(args, 'seed', 0) or 0, rank=int(os.environ.get('RANK', 0)))
     val = RoiTransform(args.resize, norm, vflip and '+V' in flip, hflip and '+V' in flip, rot90=rot90 == '+V', pad=pad)
     return train, val
 
@@ -601,11 +687,12 @@ class IfcbBinDataset(Dataset):
 
 # ------------------------------------------------------------------------------------------ batching
 def collate_rois(items):
-    """DataLoader collate_fn: [( (img_u8, flip[, turn[, fb, fc]]), *rest )] -> (roi_batch dict, *rest lists).  One ragged u8 blob,
+    """DataLoader collate_fn: [( (img_u8, flip[, turn[, fb, fc[, sigma]]]), *rest )] -> (roi_batch dict, *rest lists).  One ragged u8 blob,
     an int64 offset table and int32 dims; tensors are pinned by the loader (pin_memory=True).  ``turn`` (items of a dataset whose
     transform has rot90 set) marks the batch for the quarter-turn kernels whatever codes were drawn.  ``fb`` / ``fc`` (items of a
     dataset whose transform has jitter set) become float32 ``brightness`` / ``contrast`` tensors, each present only when some item
-    carries that factor (an item without it counts as 1)."""
+    carries that factor (an item without it counts as 1).  ``sigma`` (items of a dataset whose transform has blur set) becomes the
+    float32 ``blur`` tensor, present only when some item's sigma is not 0."""
     imgs = [it[0][0] for it in items]
     flips = [it[0][1] for it in items]
     turn = any(len(it[0]) > 2 and it[0][2] for it in items)
@@ -626,6 +713,8 @@ def collate_rois(items):
     for key, k in (('brightness', 3), ('contrast', 4)):
         if any(len(it[0]) > k and it[0][k] is not None for it in items):
             batch[key] = torch.tensor([it[0][k] if len(it[0]) > k and it[0][k] is not None else 1.0 for it in items], dtype=torch.float32)
+    if any(len(it[0]) > 5 and it[0][5] for it in items):
+        batch['blur'] = torch.tensor([it[0][5] if len(it[0]) > 5 else 0.0 for it in items], dtype=torch.float32)
     rest = list(zip(*[it[1:] for it in items]))
     out = [batch]
     for r in rest:
@@ -636,7 +725,8 @@ def collate_rois(items):
 
 def rois_to_device(batch, device, transform=None):
     """upload a collated ROI batch (u8 blob + tables) and attach Normalize parameters, the transform's ``pad`` (when set) and the
-    batch's jitter factors (when it carries any): ``jitter=(brightness, contrast)``, device tensors or None."""
+    batch's jitter factors (when it carries any): ``jitter=(brightness, contrast)``, device tensors or None; likewise ``blur``, the
+    device tensor of the batch's sigmas."""
     kw = dict(pixels=batch['pixels'].to(device, non_blocking=True), offs=batch['offs'].to(device, non_blocking=True),
               hs=batch['hs'].to(device, non_blocking=True), ws=batch['ws'].to(device, non_blocking=True),
               max_h=batch['max_h'], max_w=batch['max_w'], in_channels=batch['in_channels'])
@@ -658,6 +748,8 @@ def attach_draws(kw, batch, device, transform=None):
         kw['pad'] = transform.pad
     if 'brightness' in batch or 'contrast' in batch:
         kw['jitter'] = tuple(batch[k].to(device, non_blocking=True) if k in batch else None for k in ('brightness', 'contrast'))
+    if 'blur' in batch:
+        kw['blur'] = batch['blur'].to(device, non_blocking=True)
     return kw
 
 
@@ -769,12 +861,16 @@ class ResidentSet:
 
 def draw_items(transform, n):
     """the per-item draws of n items in batch order, by the very calls ``NeustonDataset.__getitem__`` makes (``flip_code()``, then
-    ``jitter_factors()`` when jitter is set), as the ``flips`` / ``turn`` / ``brightness`` / ``contrast`` entries ``collate_rois`` builds
+    ``jitter_factors()`` when jitter is set, ``blur_sigma()`` when blur is), as the ``flips`` / ``turn`` / ``brightness`` / ``contrast`` /
+    ``blur`` entries ``collate_rois`` builds
     from such items: a ``--resident`` run and a ``--loaders 0`` run of the same command consume identical random streams."""
     items = []
     for _ in range(n):
         flip = transform.flip_code() if transform is not None else 0
-        if transform is not None and getattr(transform, 'jitter', None) is not None:
+        if transform is not None and getattr(transform, 'blur', None) is not None:
+            fbc = transform.jitter_factors() if getattr(transform, 'jitter', None) is not None else (None, None)
+            items.append((flip, bool(getattr(transform, 'rot90', False))) + fbc + (transform.blur_sigma(),))
+        elif transform is not None and getattr(transform, 'jitter', None) is not None:
             items.append((flip, bool(getattr(transform, 'rot90', False))) + transform.jitter_factors())
         elif transform is not None and getattr(transform, 'rot90', False):
             items.append((flip, True))
@@ -786,4 +882,6 @@ def draw_items(transform, n):
     for key, k in (('brightness', 2), ('contrast', 3)):
         if any(len(it) > k and it[k] is not None for it in items):
             out[key] = torch.tensor([it[k] if len(it) > k and it[k] is not None else 1.0 for it in items], dtype=torch.float32)
+    if any(len(it) > 4 and it[4] for it in items):
+        out['blur'] = torch.tensor([it[4] if len(it) > 4 else 0.0 for it in items], dtype=torch.float32)
     return out

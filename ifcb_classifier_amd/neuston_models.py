@@ -313,6 +313,11 @@ class NeustonModel(nn.Module):
         mp = getattr(hparams, 'mix_prob', None)
         self.mix_prob = 1.0 if mp is None else float(mp)
         self.batch_mix = None             # a neuston_data.BatchMix: fit_batch / fit_batch_ddp then mix every batch they load
+        # additive (TRAIN --blur / --blur-prob): Gaussian defocus of the training images; the engine holds the run's window radius and
+        # blurs a loaded batch whose ``load_rois`` arguments carry sigmas.  Absent (older files) = off.  Recorded for information: RUN,
+        # validation and the ONNX export never blur
+        from .neuston_data import blur_radius, parse_blur
+        self.blur = parse_blur(getattr(hparams, 'blur', None))
         # additive (TRAIN --ema DECAY): the engine averages the weights inside its fused optimizer step (always with the warm-up); the
         # fit loop validates, stops, picks and saves the averaged model.  Absent (older files) = off.  The fused path only: the
         # reference hooks (training_step + a torch optimizer) write P from outside, which restarts the average
@@ -329,6 +334,9 @@ class NeustonModel(nn.Module):
         ds = getattr(hparams, 'distill', None)
         da, dt = getattr(hparams, 'distill_alpha', None), getattr(hparams, 'distill_temperature', None)
         self.distill = None if not ds else (0.5 if da is None else float(da), 4.0 if dt is None else float(dt))
+        if self.blur is not None and self.distill is not None:
+            raise ValueError('blur and distill do not combine: the teacher resizes the ROIs itself, at its own input side, and blurring '
+                             'its batch alike is not implemented')
         self.teacher = None               # a NeustonModel in inference form (attach_teacher)
         self._teacher_ready = False       # the teacher's current input slot holds the student's current batch
         self.model = get_namebrand_model(hparams.MODEL, len(hparams.classes), hparams.pretrained, device, mb,
@@ -339,6 +347,7 @@ class NeustonModel(nn.Module):
                                          label_smoothing=ls, focal_gamma=fg, mix=self.mixup > 0 or self.cutmix > 0,
                                          **({} if self.ema is None else {'ema_decay': self.ema}),
                                          **({} if self.clip_grad is None else {'clip_grad': self.clip_grad}),
+                                         **({} if self.blur is None else {'blur_radius': blur_radius(self.blur)}),
                                          **({} if self.distill is None else {'distill': self.distill}))
         # what upstream would have written at neuston_models.py:55; the engine's fused loss ops compute the same weighted, smoothed mean
         eng = self.model.engine
@@ -428,7 +437,7 @@ class NeustonModel(nn.Module):
         """the teacher's ``load_rois`` arguments for a batch the student loads with ``kw``: the same ROIs and per-ROI flip / turn codes,
         resized to the teacher's S with the teacher file's img_norm and pad.  Never the jitter factors: ifcbk_roi_jitter maps ``pixels``
         IN PLACE, so the student's load has jittered the blob by the time the teacher reads it, and a second pass would jitter it twice."""
-        out = {k: v for k, v in kw.items() if k not in ('mean', 'std', 'pad', 'jitter', 'slot')}
+        out = {k: v for k, v in kw.items() if k not in ('mean', 'std', 'pad', 'jitter', 'blur', 'slot')}
         out.update(self._teacher_load)
         return out
 

@@ -22,7 +22,7 @@ from torch.utils.data import DataLoader
 
 from .neuston_callbacks import SaveValidationResults, SaveTestResults
 from .neuston_data import (get_trainval_datasets, IfcbBinDataset, ImageDataset, IMG_EXTENSIONS, collate_rois,
-                           jitter_arg, mix_alpha_arg, mix_prob_arg, pad_arg, rois_to_device)
+                           blur_arg, blur_prob_arg, jitter_arg, mix_alpha_arg, mix_prob_arg, pad_arg, rois_to_device)
 from .neuston_models import NeustonModel, check_teacher_classes, load_checkpoint_file, load_pretrained_weights
 
 
@@ -442,6 +442,14 @@ def do_training(args):
                              'output_scores confusion_matrix counts_perclass f1_perclass f1_weighted f1_macro'.split()]
     callbacks = [SaveValidationResults(outdir=args.outdir, outfile=rf[0], series=rf[1:]) for rf in args.result_files]
     args.seed = seed_everything(args.seed or None)
+    if getattr(args, 'blur', None) is None:
+        # unset: the model file and args.yml carry no blur entry at all
+        for k in ('blur', 'blur_prob'):
+            if hasattr(args, k):
+                delattr(args, k)
+    elif getattr(args, 'distill', None):
+        raise SystemExit('TRAIN --blur and --distill do not combine: the teacher resizes the ROIs itself, at its own input side, and '
+                         'would see sharp images where the student sees blurred ones; blurring the teacher\'s batch alike is not implemented')
 
     training_dataset, validation_dataset = get_trainval_datasets(args)
     assert training_dataset.classes == validation_dataset.classes
@@ -744,6 +752,8 @@ def argparse_nn_train(train_subparser):
     augs.add_argument('--mixup', metavar='ALPHA', type=mix_alpha_arg, default=0.0, action=_ExclusiveLossScalar, help='(MI355X path, additive) Mixup of the training batches, as timm\'s Mixup in batch mode: per batch lam ~ Beta(ALPHA, ALPHA), every image becomes lam * image + (1 - lam) * partner, the partner being the image at the mirrored place of the batch, and the loss takes both labels with weights lam and 1 - lam. Mixed on the GPU after the resize. A finite float > 0; composes with --class-norm and --label-smoothing, not with --focal-gamma; val_loss stays unmixed. Default is 0 (off)')
     augs.add_argument('--cutmix', metavar='ALPHA', type=mix_alpha_arg, default=0.0, action=_ExclusiveLossScalar, help='(MI355X path, additive) CutMix of the training batches, as timm\'s Mixup(cutmix_alpha=ALPHA) in batch mode: per batch a box covering about 1 - Beta(ALPHA, ALPHA) of the image is filled from the partner image, and lam is the share left outside the box. With --mixup as well, each batch is CutMix with probability 0.5, else Mixup. A finite float > 0; not with --focal-gamma. Default is 0 (off)')
     augs.add_argument('--mix-prob', metavar='P', type=mix_prob_arg, default=1.0, help='(MI355X path, additive) Probability that a training batch is mixed at all by --mixup / --cutmix. A float in [0, 1]. Default is 1')
+    augs.add_argument('--blur', metavar='SIGMA_MAX', type=blur_arg, default=None, help='(MI355X path, additive) Gaussian defocus of the training images, as transforms.GaussianBlur(k, sigma=(0.1, SIGMA_MAX)) behind the resize: each image is blurred with probability --blur-prob, with sigma uniform in [0.1, SIGMA_MAX], by a window of radius ceil(3*SIGMA_MAX) (k = 2*radius+1) with reflected borders, on the GPU. SIGMA_MAX is a float in (0.1, 4]. Training set only; not with --distill. Default (unset) is no blur')
+    augs.add_argument('--blur-prob', metavar='P', type=blur_prob_arg, default=0.5, help='(MI355X path, additive) Probability that a training image is blurred at all by --blur. A float in [0, 1]. Default is 0.5')
     out = t.add_argument_group(title='Output Options')
     out.add_argument('--outdir', default='training-output/{TRAIN_ID}', help='Default is "training-output/{TRAIN_ID}"')
     out.add_argument('--model-id', default='{TRAIN_ID}', help='Set a specific model id. Patterns {TRAIN_DATE} and {TRAIN_ID} are recognized. Default is "{TRAIN_ID}"')

@@ -420,6 +420,19 @@ IFCBK_API int ifcbk_roi_gather(ifcbk_ctx*, const uint8_t* src_pixels, const int6
 #define IFCBK_MIX_U8 2
 IFCBK_API int ifcbk_batch_mix(ifcbk_ctx*, void* x, int kind /* IFCBK_MIX_U8 | IFCBK_BF16 | IFCBK_F32 */, int N, int S,
                          const float* lam /*[N], device*/, int y0, int y1, int x0, int x1, void* stream);
+/* Gaussian defocus of a RESIZED batch, in place (TRAIN --blur; torchvision's GaussianBlur at kernel_size 2 radius + 1 with one sigma
+ * per image).  x and kind as ifcbk_batch_mix: the u8 plane [N][S][S] (kind = IFCBK_MIX_U8; any address) or the dense tensor
+ * [N][S][S][8] (kind = IFCBK_BF16 / IFCBK_F32; 16-byte aligned), of which channels 0..2 are blurred and 3..7 keep their bits.  Per
+ * image n the weights are w[j] = expf(-0.5 ((j - radius) / sigma[n])^2), j = 0..2 radius, divided by their sum (fp32, taken in
+ * ascending j); the image becomes its 2-D convolution with w (x) w, computed separably -- rows first -- as fmaf chains in ascending j,
+ * with torch's 'reflect' border (-1 -> 1, S -> S - 2).  The fp32 result is stored as rint (nearest-even) clamped to 0..255, as
+ * round-to-nearest-even bf16, or as fp32.  sigma[n] == 0 -- and a sigma that is negative or not finite -- leaves image n's bits alone.
+ * An image's result depends on its own pixels and sigma only and is reproducible bit for bit; no byte outside the N images is read or
+ * written; no workspace.  IFCBK_EINVAL: x or sigma NULL, N < 1, radius outside 1..12, radius >= S, an unknown kind, a dense tensor
+ * that is not 16-byte aligned, an S whose LDS rows do not fit 64 KiB: (64 + 4 (S + 2 radius) + (2 radius + 4) S) * 4 > 65536 bytes
+ * (S > 507 at radius 12). */
+IFCBK_API int ifcbk_batch_blur(ifcbk_ctx*, void* x, int kind /* IFCBK_MIX_U8 | IFCBK_BF16 | IFCBK_F32 */, int N, int S,
+                         const float* sigma /*[N], device*/, int radius /* 1..12, < S */, void* stream);
 /* one symmetry of the square applied to every image of a RESIZED batch, in place (RUN --tta: the views of test-time augmentation are
  * taken where the batch lies, so the eval programs and their captured graphs keep their pointers).  x and kind as ifcbk_batch_mix:
  * the u8 plane [N][S][S] (kind = IFCBK_MIX_U8; any address) or the dense tensor [N][S][S][8] (kind = IFCBK_BF16 / IFCBK_F32; 16-byte
