@@ -298,3 +298,23 @@ def pad_fill(pad):
     if isinstance(pad, bool) or not isinstance(pad, int) or not 0 <= pad <= 255:
         raise ValueError("pad must be None, 'border' or an integer 0..255, got %r" % (pad,))
     return int(pad)
+
+
+def roi_resize(n, S, in_channels, dtype, flips=None, turn=False, mean=None, std=None, transform_input=False, pad=None):
+    """-> (d, fn, fill): the RoiDesc of a resize of ``n`` ROIs to S x S and the entry point that takes it -- ifcbk_roi_preprocess with
+    no extra argument, or for a ``pad`` setting ifcbk_roi_preprocess_fit with its fill.  flips: the per-ROI codes or None; turn: they
+    may hold bit 2 = transpose; mean / std: Normalize, None = (0, 1); transform_input: torchvision's inception_v3 re-normalisation."""
+    d = RoiDesc()
+    d.n_img, d.S, d.in_channels, d.out_channels = n, S, in_channels, 8
+    d.flip_bits_valid = (2 if turn else 1) if flips is not None else 0
+    d.dtype = dtype
+    for k in range(3):
+        d.mean[k] = 0.0 if mean is None else float(mean[k])
+        d.std[k] = 1.0 if std is None else float(std[k])
+        d.tin_scale[k], d.tin_shift[k] = 1.0, 0.0
+    if transform_input:
+        for k, (s, m) in enumerate(((0.229, 0.485), (0.224, 0.456), (0.225, 0.406))):
+            d.tin_scale[k], d.tin_shift[k] = s / 0.5, (m - 0.5) / 0.5
+    if pad is None:
+        return d, 'ifcbk_roi_preprocess', ()
+    return d, 'ifcbk_roi_preprocess_fit', (pad_fill(pad),)

@@ -13,7 +13,7 @@ import os
 import torch
 
 from . import _lib, ops
-from ._lib import Op, ConvDesc, BnDesc, PoolDesc, HeadDesc, RoiDesc, pad_fill
+from ._lib import Op, ConvDesc, BnDesc, PoolDesc, HeadDesc
 from .plan import OpList, Program, PlanBuilder, schedule_lanes, _overlap, _vp       # noqa: F401  (re-exported: tests import them from here)
 
 # operand slots the engine reads back from ops of a plan
@@ -78,6 +78,12 @@ def check_distill(distill, focal_gamma=0.0, mix=False):
     if mix:
         raise ValueError('distill and mix do not combine: give one of them')
     return alpha, T
+
+
+def _per_roi_f32(t, n, device, message):
+    """refuse (ValueError ``message`` % (n, device)) what is not a contiguous float32 tensor of one value per ROI on the ROIs' device"""
+    if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.device == device and t.numel() == n and t.is_contiguous()):
+        raise ValueError(message % (n, device))
 
 
 class Engine:
@@ -1009,54 +1015,47 @@ class Engine:
         blurs the RESIZED batch in place with the engine's ``blur_radius``, behind the resize on the same ctx and stream, on whichever
         buffer the resize wrote (the u8 plane or the dense tensor), so plans and captured graphs keep their addresses; a ``mix_batch``
         of the slot comes after it.  Without ``blur`` nothing more is launched."""
+        n = hs.numel()
         if blur is not None:
-            n = hs.numel()
             if self.blur_radius is None:
                 raise RuntimeError('load_rois(blur=): this engine was built without blur_radius')
-            if not (torch.is_tensor(blur) and blur.dtype == torch.float32 and blur.device == pixels.device and blur.numel() == n
-                    and blur.is_contiguous()):
-                raise ValueError('blur: a float32 tensor of %d sigmas on %s, or None' % (n, pixels.device))
-        if slot is not None:
-            ctx, stream, s = self.pre_ctx, C.c_void_p(self.pre_stream.cuda_stream), slot
-            n = self._load_rois_into(ctx, stream, s, False, pixels, offs, hs, ws, max_h, max_w, in_channels, flips, mean, std, turn, pad, jitter)
-        else:
-            ctx, stream, s = self.ctx, self.stream(), self.in_slot
-            n = self._load_rois_into(ctx, stream, s, True, pixels, offs, hs, ws, max_h, max_w, in_channels, flips, mean, std, turn, pad, jitter)
+            _per_roi_f32(blur, n, pixels.device, 'blur: a float32 tensor of %d sigmas on %s, or None')
+        target = self._slot_target(slot)
+        ctx, stream, _, s, _ = target
+        self._load_rois_into(target, pixels, offs, hs, ws, max_h=max_h, max_w=max_w, in_channels=in_channels, flips=flips, mean=mean,
+                             std=std, turn=turn, pad=pad, jitter=jitter)
         if blur is not None:
-            if self.in_kind[s] == 'u8':
-                buf, kind = self.in_u8[s], _lib.MIX_U8
-            else:
-                buf, kind = self.in_bufs[s], self.cdtype
+            buf, kind = self._slot_image(s)
             ctx.call('ifcbk_batch_blur', _vp(buf), kind, n, self.net.S, _vp(blur), self.blur_radius, stream)
         return n
 
-    def _load_rois_into(self, ctx, stream, slot, main, pixels, offs, hs, ws, max_h, max_w, in_channels, flips, mean, std, turn=False, pad=None,
-                        jitter=None):
+    def _slot_target(self, slot):
+        """where a call on an input slot runs -> (ctx, stream handle, torch stream, slot, main).  slot None: the current slot, on the
+        engine's own context and the current stream (main = True); else a prefetch slot, on the prefetch context and stream"""
+        if slot is not None:
+            return self.pre_ctx, C.c_void_p(self.pre_stream.cuda_stream), self.pre_stream, slot, False
+        cur = torch.cuda.current_stream(self.dev)
+        return self.ctx, C.c_void_p(cur.cuda_stream), cur, self.in_slot, True
+
+    def _slot_image(self, s):
+        """(buf, kind) of the batch in input slot ``s`` for the in-place batch kernels: whichever buffer the slot's load wrote, the u8
+        plane or the dense tensor"""
+        if self.in_kind[s] == 'u8':
+            return self.in_u8[s], _lib.MIX_U8
+        return self.in_bufs[s], self.cdtype
+
+    def _load_rois_into(self, target, pixels, offs, hs, ws, *, max_h, max_w, in_channels, flips, mean, std, turn, pad, jitter):
+        """the body of ``load_rois`` on a ``_slot_target``: workspace growth, the in-place jitter, the resize"""
+        ctx, stream, tstream, slot, main = target
         n = hs.numel()
-        dst = self.in_bufs[slot]
-        d = RoiDesc()
-        d.n_img, d.S, d.in_channels, d.out_channels = n, self.net.S, in_channels, 8
-        d.flip_bits_valid = (2 if turn else 1) if flips is not None else 0
-        d.dtype = self.cdtype
-        for k in range(3):
-            d.mean[k] = 0.0 if mean is None else float(mean[k])
-            d.std[k] = 1.0 if std is None else float(std[k])
-            d.tin_scale[k], d.tin_shift[k] = 1.0, 0.0
-        if self.net.transform_input:
-            for k, (s, m) in enumerate(((0.229, 0.485), (0.224, 0.456), (0.225, 0.406))):
-                d.tin_scale[k], d.tin_shift[k] = s / 0.5, (m - 0.5) / 0.5
-        if pad is None:
-            fn, fill = 'ifcbk_roi_preprocess', ()
-        else:
-            fn, fill = 'ifcbk_roi_preprocess_fit', (pad_fill(pad),)
+        d, fn, fill = _lib.roi_resize(n, self.net.S, in_channels, self.cdtype, flips, turn, mean, std, self.net.transform_input, pad)
         need = getattr(ctx.lib, fn + '_workspace')(C.byref(d), int(max_h), int(max_w))
         if jitter is not None and jitter[0] is None and jitter[1] is None:
             jitter = None
         if jitter is not None:
             for f in jitter:
-                if f is not None and not (torch.is_tensor(f) and f.dtype == torch.float32 and f.device == pixels.device and f.numel() == n
-                                          and f.is_contiguous()):
-                    raise ValueError('jitter: (brightness, contrast) are float32 tensors of %d factors on %s, or None' % (n, pixels.device))
+                if f is not None:
+                    _per_roi_f32(f, n, pixels.device, 'jitter: (brightness, contrast) are float32 tensors of %d factors on %s, or None')
             need = max(need, ctx.lib.ifcbk_roi_jitter_workspace(n))
         if need > ctx.lib.ifcbk_ctx_workspace_bytes(ctx.h):
             if not main:
@@ -1066,23 +1065,19 @@ class Engine:
             # in place on the uploaded blob, stream-ordered in front of the resize (its sums lie where the resize puts its tables)
             ctx.call('ifcbk_roi_jitter', _vp(pixels), _vp(offs), _vp(hs), _vp(ws), n, int(in_channels), int(max_h), int(max_w),
                      _vp(jitter[0]), _vp(jitter[1]), _vp(pixels), stream)
-        if self.stem_u8 is not None and in_channels == 1:
+        u8 = self.stem_u8 is not None and in_channels == 1
+        if u8:
             # grey ROIs: only the resized u8 plane is written; x_c = a_c * g + b_c (ToTensor, Normalize, transform_input) goes to the
             # stem conv as six floats
             ab = tuple(d.tin_scale[k] / (255.0 * d.std[k]) for k in range(3)) + \
                 tuple(d.tin_shift[k] - d.tin_scale[k] * d.mean[k] / d.std[k] for k in range(3))
             if self._in_ab_host[slot] != ab:
-                with torch.cuda.stream(torch.cuda.current_stream(self.dev) if main else self.pre_stream):
+                with torch.cuda.stream(tstream):
                     self.in_ab[slot].copy_(torch.tensor(ab, dtype=torch.float32), non_blocking=False)
                 self._in_ab_host[slot] = ab
-            ctx.call(fn, C.byref(d), _vp(pixels), _vp(offs), _vp(hs), _vp(ws), _vp(flips),
-                     int(max_h), int(max_w), *fill, None, _vp(self.in_u8[slot]), stream)
-            self.in_kind[slot] = 'u8'
-            return n
-        ctx.call(fn, C.byref(d), _vp(pixels), _vp(offs), _vp(hs), _vp(ws), _vp(flips),
-                 int(max_h), int(max_w), *fill, _vp(dst), None, stream)
-        self.in_kind[slot] = 'nhwc'
-        return n
+        ctx.call(fn, C.byref(d), _vp(pixels), _vp(offs), _vp(hs), _vp(ws), _vp(flips), int(max_h), int(max_w), *fill,
+                 None if u8 else _vp(self.in_bufs[slot]), _vp(self.in_u8[slot]) if u8 else None, stream)
+        self.in_kind[slot] = 'u8' if u8 else 'nhwc'
 
     def mix_batch(self, n, lam, box=None, slot=None):
         """mix the ``n`` loaded images of an input slot with their reverse, in place (TRAIN --mixup / --cutmix; timm's Mixup, batch mode):
@@ -1095,10 +1090,7 @@ class Engine:
         n = int(n)
         if not 1 <= n <= self.max_batch:
             raise ValueError('mix_batch: n %d outside 1..%d' % (n, self.max_batch))
-        if slot is not None:
-            ctx, stream, tstream, s = self.pre_ctx, C.c_void_p(self.pre_stream.cuda_stream), self.pre_stream, slot
-        else:
-            ctx, stream, tstream, s = self.ctx, self.stream(), torch.cuda.current_stream(self.dev), self.in_slot
+        ctx, stream, tstream, s, _ = self._slot_target(slot)
         y0, y1, x0, x1 = (0, 0, 0, 0) if box is None else (int(v) for v in box)
         with torch.cuda.stream(tstream):
             if torch.is_tensor(lam):
@@ -1107,10 +1099,7 @@ class Engine:
                 self.mix_lam[s][:n].copy_(lam.reshape(n), non_blocking=True)
             else:
                 self.mix_lam[s][:n].fill_(float(lam))
-        if self.in_kind[s] == 'u8':
-            buf, kind = self.in_u8[s], _lib.MIX_U8
-        else:
-            buf, kind = self.in_bufs[s], self.cdtype
+        buf, kind = self._slot_image(s)
         ctx.call('ifcbk_batch_mix', _vp(buf), kind, n, self.net.S, _vp(self.mix_lam[s]), y0, y1, x0, x1, stream)
         return n
 
@@ -1128,14 +1117,8 @@ class Engine:
         n = int(n)
         if not 1 <= n <= self.max_batch:
             raise ValueError('sym_batch: n %d outside 1..%d' % (n, self.max_batch))
-        if slot is not None:
-            ctx, stream, s = self.pre_ctx, C.c_void_p(self.pre_stream.cuda_stream), slot
-        else:
-            ctx, stream, s = self.ctx, self.stream(), self.in_slot
-        if self.in_kind[s] == 'u8':
-            buf, kind = self.in_u8[s], _lib.MIX_U8
-        else:
-            buf, kind = self.in_bufs[s], self.cdtype
+        ctx, stream, _, s, _ = self._slot_target(slot)
+        buf, kind = self._slot_image(s)
         ctx.call('ifcbk_batch_sym', _vp(buf), kind, n, self.net.S, int(op), stream)
         return n
 

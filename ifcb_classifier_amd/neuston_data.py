@@ -88,33 +88,66 @@ class RoiTransform:
             return 0.0
         return float(np.float32(BLUR_SIGMA_MIN + v * (self.blur - BLUR_SIGMA_MIN)))
 
+    def draw_item(self):
+        """one item's random draws, in the order every feed makes them -- ``flip_code()``, then ``jitter_factors()`` with jitter set, then
+        ``blur_sigma()`` with blur set -- as the tail of its tuple behind the image: (flip[, turn[, fb, fc[, sigma]]]).  turn: this
+        transform turns, whatever the draw was; fb, fc: the brightness and contrast factors, None without jitter or for a zero range;
+        sigma: 0.0 = not blurred.  A later field brings the earlier ones along; ``collate_draws`` reads them."""
+        tail = (self.flip_code(), self.rot90)
+        if self.blur is not None:
+            return tail + self.jitter_factors() + (self.blur_sigma(),)      # (without jitter the factors are (None, None), nothing drawn)
+        if self.jitter is not None:
+            return tail + self.jitter_factors()
+        return tail if self.rot90 else tail[:1]
+
 
 BLUR_SIGMA_MIN = 0.1          # torchvision's default low end of GaussianBlur's sigma range
 BLUR_SIGMA_LIMIT = 4.0        # the largest SIGMA_MAX: radius ceil(3 * 4) = 12, the kernel's largest window
+
+
+def _floats(values, expected, ok=None, wrong=None):
+    """the body the option parsers share: refuse a bool (ValueError ``expected``), ``float()`` every value, then hold each one to
+    ``ok`` (ValueError ``wrong``) -> the list of floats"""
+    if any(isinstance(v, bool) for v in values):
+        raise ValueError(expected)
+    out = [float(v) for v in values]                                    # (float('a') raises ValueError too)
+    if ok is not None and not all(ok(v) for v in out):                  # (nan fails every comparison)
+        raise ValueError(wrong)
+    return out
+
+
+def _arg_type(parse, message):
+    """argparse ``type=`` of an option (neuston_net TRAIN, neuston_util CALC_IMG_NORM): ``parse``, its ValueError reworded as ``message``"""
+    def arg(text):
+        import argparse
+        try:
+            return parse(text)
+        except ValueError:
+            raise argparse.ArgumentTypeError(message % text)
+    return arg
+
+
+def _unit(v):
+    return 0.0 <= v <= 1.0
+
+
+def _finite(v):
+    return 0.0 <= v < float('inf')
 
 
 def parse_blur(value):
     """``--blur SIGMA_MAX`` / a checkpoint's ``blur``: None (unset) or a finite float in (0.1, 4]"""
     if value is None:
         return None
-    if isinstance(value, bool):
-        raise ValueError('blur: SIGMA_MAX expected, got %r' % (value,))
-    v = float(value)                                                    # (float('a') raises ValueError too)
-    if not BLUR_SIGMA_MIN < v <= BLUR_SIGMA_LIMIT:                      # (nan fails both comparisons)
-        raise ValueError('blur: SIGMA_MAX must be a float in (0.1, 4], got %r' % (value,))
-    return v
+    return _floats([value], 'blur: SIGMA_MAX expected, got %r' % (value,), lambda v: BLUR_SIGMA_MIN < v <= BLUR_SIGMA_LIMIT,
+                   'blur: SIGMA_MAX must be a float in (0.1, 4], got %r' % (value,))[0]
 
 
 def parse_blur_prob(value):
     """``--blur-prob P`` / a checkpoint's ``blur_prob``: None -> 0.5, else a float in [0, 1]"""
     if value is None:
         return 0.5
-    if isinstance(value, bool):
-        raise ValueError('blur-prob: P expected, got %r' % (value,))
-    v = float(value)
-    if not 0.0 <= v <= 1.0:                                             # (nan fails both comparisons)
-        raise ValueError('blur-prob: P must be in [0, 1], got %r' % (value,))
-    return v
+    return _floats([value], 'blur-prob: P expected, got %r' % (value,), _unit, 'blur-prob: P must be in [0, 1], got %r' % (value,))[0]
 
 
 def blur_radius(sigma_max):
@@ -122,24 +155,6 @@ def blur_radius(sigma_max):
     import math
     sigma_max = parse_blur(sigma_max)
     return None if sigma_max is None else int(math.ceil(3.0 * sigma_max))
-
-
-def blur_arg(text):
-    """argparse ``type=`` of ``--blur SIGMA_MAX`` (neuston_net TRAIN)"""
-    import argparse
-    try:
-        return parse_blur(text)
-    except ValueError:
-        raise argparse.ArgumentTypeError('SIGMA_MAX must be a float in (0.1, 4], got %r' % text)
-
-
-def blur_prob_arg(text):
-    """argparse ``type=`` of ``--blur-prob P`` (neuston_net TRAIN)"""
-    import argparse
-    try:
-        return parse_blur_prob(text)
-    except ValueError:
-        raise argparse.ArgumentTypeError('P must be a float in [0, 1], got %r' % text)
 
 
 def parse_jitter(value):
@@ -153,21 +168,11 @@ def parse_jitter(value):
         parts = list(value)
     else:
         parts = [value]
-    if not 1 <= len(parts) <= 2 or any(isinstance(v, bool) for v in parts):
-        raise ValueError('jitter: B[,C] expected, got %r' % (value,))
-    bc = [float(v) for v in parts] + [0.0] * (2 - len(parts))           # (float('a') raises ValueError too)
-    if not all(0.0 <= v < float('inf') for v in bc):                   # (nan fails both comparisons)
-        raise ValueError('jitter: B and C must be finite and not negative, got %r' % (value,))
+    expected = 'jitter: B[,C] expected, got %r' % (value,)
+    if not 1 <= len(parts) <= 2:
+        raise ValueError(expected)
+    bc = _floats(parts, expected, _finite, 'jitter: B and C must be finite and not negative, got %r' % (value,)) + [0.0] * (2 - len(parts))
     return bc if any(bc) else None
-
-
-def jitter_arg(text):
-    """argparse ``type=`` of ``--jitter B[,C]`` (neuston_net TRAIN)"""
-    import argparse
-    try:
-        return parse_jitter(text)
-    except ValueError:
-        raise argparse.ArgumentTypeError('B[,C] must be one or two finite floats >= 0, got %r' % text)
 
 
 def parse_mix_alpha(value, name='mixup'):
@@ -175,42 +180,15 @@ def parse_mix_alpha(value, name='mixup'):
     finite float > 0, the parameter of the Beta(ALPHA, ALPHA) draw"""
     if value is None:
         return 0.0
-    if isinstance(value, bool):
-        raise ValueError('%s: ALPHA expected, got %r' % (name, value))
-    v = float(value)                                                    # (float('a') raises ValueError too)
-    if not 0.0 <= v < float('inf'):                                     # (nan fails both comparisons)
-        raise ValueError('%s: ALPHA must be a finite float >= 0 (0 = off), got %r' % (name, value))
-    return v
+    return _floats([value], '%s: ALPHA expected, got %r' % (name, value), _finite,
+                   '%s: ALPHA must be a finite float >= 0 (0 = off), got %r' % (name, value))[0]
 
 
 def parse_mix_prob(value):
     """``--mix-prob P`` / a checkpoint's ``mix_prob``: None -> 1.0, else a float in [0, 1]"""
     if value is None:
         return 1.0
-    if isinstance(value, bool):
-        raise ValueError('mix-prob: P expected, got %r' % (value,))
-    v = float(value)
-    if not 0.0 <= v <= 1.0:                                             # (nan fails both comparisons)
-        raise ValueError('mix-prob: P must be in [0, 1], got %r' % (value,))
-    return v
-
-
-def mix_alpha_arg(text):
-    """argparse ``type=`` of ``--mixup ALPHA`` and ``--cutmix ALPHA`` (neuston_net TRAIN)"""
-    import argparse
-    try:
-        return parse_mix_alpha(text)
-    except ValueError:
-        raise argparse.ArgumentTypeError('ALPHA must be a finite float >= 0 (0 = off), got %r' % text)
-
-
-def mix_prob_arg(text):
-    """argparse ``type=`` of ``--mix-prob P`` (neuston_net TRAIN)"""
-    import argparse
-    try:
-        return parse_mix_prob(text)
-    except ValueError:
-        raise argparse.ArgumentTypeError('P must be a float in [0, 1], got %r' % text)
+    return _floats([value], 'mix-prob: P expected, got %r' % (value,), _unit, 'mix-prob: P must be in [0, 1], got %r' % (value,))[0]
 
 
 def cut_box(lam0, cy, cx, S):
@@ -258,16 +236,10 @@ def parse_affine(rotate=None, translate=None, scale=None):
     """the ranges of a random affine (``RandomAffine(degrees=DEG, translate=(T, T), scale=(LO, HI))``) -> None (nothing set: also for
     0, 0 and 1:1) or (DEG, T, LO, HI).  Host arithmetic only so far: no kernel applies the draw yet, and TRAIN has no flag for it.  DEG finite and >= 0, 0 <= T <= 1, 0.25 <= LO <= HI <= 4: with these every matrix a draw can give stays inside
     the range of Pillow's 16.16 fixed-point routine.  scale: None, a 'LO:HI' string, one number (LO = HI) or a (LO, HI) pair."""
-    def num(v, what):
-        if isinstance(v, bool):
-            raise ValueError('%s: a number expected, got %r' % (what, v))
-        return float(v)                                                 # (float('a') raises ValueError too)
-    deg = 0.0 if rotate is None else num(rotate, 'rotate')
-    if not 0.0 <= deg < float('inf'):                                   # (nan fails both comparisons)
-        raise ValueError('rotate: DEG must be finite and not negative, got %r' % (rotate,))
-    t = 0.0 if translate is None else num(translate, 'translate')
-    if not 0.0 <= t <= 1.0:
-        raise ValueError('translate: FRAC must be in [0, 1], got %r' % (translate,))
+    def num(v, what, ok=None, wrong=None):
+        return _floats([v], '%s: a number expected, got %r' % (what, v), ok, wrong)[0]
+    deg = 0.0 if rotate is None else num(rotate, 'rotate', _finite, 'rotate: DEG must be finite and not negative, got %r' % (rotate,))
+    t = 0.0 if translate is None else num(translate, 'translate', _unit, 'translate: FRAC must be in [0, 1], got %r' % (translate,))
     if scale is None:
         lo = hi = 1.0
     else:
@@ -368,13 +340,12 @@ def parse_pad(value):
     return v
 
 
-def pad_arg(text):
-    """argparse ``type=`` of ``--pad [FILL]`` (neuston_net TRAIN, neuston_util CALC_IMG_NORM)"""
-    import argparse
-    try:
-        return parse_pad(text)
-    except ValueError:
-        raise argparse.ArgumentTypeError('FILL must be "border" or an integer 0..255, got %r' % text)
+blur_arg = _arg_type(parse_blur, 'SIGMA_MAX must be a float in (0.1, 4], got %r')                    # --blur SIGMA_MAX
+blur_prob_arg = _arg_type(parse_blur_prob, 'P must be a float in [0, 1], got %r')                      # --blur-prob P
+jitter_arg = _arg_type(parse_jitter, 'B[,C] must be one or two finite floats >= 0, got %r')            # --jitter B[,C]
+mix_alpha_arg = _arg_type(parse_mix_alpha, 'ALPHA must be a finite float >= 0 (0 = off), got %r')      # --mixup ALPHA, --cutmix ALPHA
+mix_prob_arg = _arg_type(parse_mix_prob, 'P must be a float in [0, 1], got %r')                        # --mix-prob P
+pad_arg = _arg_type(parse_pad, 'FILL must be "border" or an integer 0..255, got %r')                   # --pad [FILL]
 
 
 def fold_turns(vflip, hflip, k):
@@ -553,18 +524,8 @@ class NeustonDataset(Dataset):
     def __getitem__(self, index):
         path = self.images[index]
         data = default_loader(path)
-        flip = self.transforms.flip_code() if self.transforms is not None else 0
-        if self.transforms is not None and getattr(self.transforms, 'blur', None) is not None:
-            # (field six: the sigma of this draw's Gaussian blur, 0.0 = none; fields four and five as below, None without jitter)
-            tr = self.transforms
-            fbc = tr.jitter_factors() if getattr(tr, 'jitter', None) is not None else (None, None)
-            return (data, flip, bool(getattr(tr, 'rot90', False))) + fbc + (tr.blur_sigma(),), self.targets[index], path
-        if self.transforms is not None and getattr(self.transforms, 'jitter', None) is not None:
-            # (fields four and five: the brightness and contrast factors of this draw, None for a zero range)
-            return (data, flip, bool(getattr(self.transforms, 'rot90', False))) + self.transforms.jitter_factors(), self.targets[index], path
-        if self.transforms is not None and getattr(self.transforms, 'rot90', False):
-            return (data, flip, True), self.targets[index], path      # (third field: the transform turns, whatever this draw was)
-        return (data, flip), self.targets[index], path
+        tail = self.transforms.draw_item() if self.transforms is not None else (0,)
+        return (data,) + tail, self.targets[index], path
 
     def __len__(self):
         return len(self.images)
@@ -620,20 +581,16 @@ def get_trainval_transforms(args):
     norm = parse_imgnorm(args.img_norm) if args.img_norm else None
     flip = args.flip or ''
     vflip, hflip = 'x' in flip, 'y' in flip                # 'x' = vertical, 'y' = horizontal (sic)
-    rot90 = getattr(args, 'rot90', None)                   # None (unset) | 'T' (training set) | '+V' (validation set as well)
-    pad = getattr(args, 'pad', None)                       # geometry, not augmentation: both sets alike
-    jitter = getattr(args, 'jitter', None)                 # photometric augmentation: the training set only
-    # batch mixing (--mixup / --cutmix): the training set only; absent or 0: no BatchMix object, no draw
-    mixup, cutmix = parse_mix_alpha(getattr(args, 'mixup', None), 'mixup'), parse_mix_alpha(getattr(args, 'cutmix', None), 'cutmix')
-    mix = None
-    if mixup > 0 or cutmix > 0:
-        mix = BatchMix(mixup, cutmix, parse_mix_prob(getattr(args, 'mix_prob', None)), seed=getattr(args, 'seed', 0) or 0,
-                       rank=int(os.environ.get('RANK', 0)))
-    # Gaussian defocus (--blur / --blur-prob): the training set only; its draws have a generator of their own
-    train = RoiTransform(args.resize, norm, vflip, hflip, rot90=bool(rot90), pad=pad, jitter=jitter, mix=mix,
-                         blur=getattr(args, 'blur', None), blur_prob=getattr(args, 'blur_prob', None),
-                         seed=getattr(args, 'seed', 0) or 0, rank=int(os.environ.get('RANK', 0)))
-    val = RoiTransform(args.resize, norm, vflip and '+V' in flip, hflip and '+V' in flip, rot90=rot90 == '+V', pad=pad)
+    # the options a caller's args may lack (None = unset).  rot90: 'T' (training set) | '+V' (validation set as well); pad: geometry,
+    # not augmentation, so both sets alike; jitter, blur and batch mixing: the training set only
+    opt = {k: getattr(args, k, None) for k in ('rot90', 'pad', 'jitter', 'mixup', 'cutmix', 'mix_prob', 'blur', 'blur_prob', 'seed')}
+    own = dict(seed=opt['seed'] or 0, rank=int(os.environ.get('RANK', 0)))      # what the blur and mix generators are seeded from
+    # absent or 0: no BatchMix object, no draw
+    mixup, cutmix = parse_mix_alpha(opt['mixup'], 'mixup'), parse_mix_alpha(opt['cutmix'], 'cutmix')
+    mix = BatchMix(mixup, cutmix, parse_mix_prob(opt['mix_prob']), **own) if mixup > 0 or cutmix > 0 else None
+    train = RoiTransform(args.resize, norm, vflip, hflip, rot90=bool(opt['rot90']), pad=opt['pad'], jitter=opt['jitter'], mix=mix,
+                         blur=opt['blur'], blur_prob=opt['blur_prob'], **own)
+    val = RoiTransform(args.resize, norm, vflip and '+V' in flip, hflip and '+V' in flip, rot90=opt['rot90'] == '+V', pad=opt['pad'])
     return train, val
 
 
@@ -686,16 +643,27 @@ class IfcbBinDataset(Dataset):
 
 
 # ------------------------------------------------------------------------------------------ batching
+def collate_draws(tails):
+    """the items' draws ``(flip[, turn[, fb, fc[, sigma]]])`` (``RoiTransform.draw_item``; a plain item has ``(flip,)``) as a batch's
+    entries: ``flips``, uint8 codes; ``turn`` = True when some item is flagged (its transform has rot90 set), which marks the batch for
+    the quarter-turn kernels whatever codes were drawn; float32 ``brightness`` / ``contrast``, each present only when some item carries
+    that factor (an item without it counts as 1); float32 ``blur``, present only when some item's sigma is not 0."""
+    out = dict(flips=torch.tensor([t[0] for t in tails], dtype=torch.uint8))
+    if any(len(t) > 1 and t[1] for t in tails):
+        out['turn'] = True
+    for key, k in (('brightness', 2), ('contrast', 3)):
+        if any(len(t) > k and t[k] is not None for t in tails):
+            out[key] = torch.tensor([t[k] if len(t) > k and t[k] is not None else 1.0 for t in tails], dtype=torch.float32)
+    if any(len(t) > 4 and t[4] for t in tails):
+        out['blur'] = torch.tensor([t[4] if len(t) > 4 else 0.0 for t in tails], dtype=torch.float32)
+    return out
+
+
 def collate_rois(items):
     """DataLoader collate_fn: [( (img_u8, flip[, turn[, fb, fc[, sigma]]]), *rest )] -> (roi_batch dict, *rest lists).  One ragged u8 blob,
-    an int64 offset table and int32 dims; tensors are pinned by the loader (pin_memory=True).  ``turn`` (items of a dataset whose
-    transform has rot90 set) marks the batch for the quarter-turn kernels whatever codes were drawn.  ``fb`` / ``fc`` (items of a
-    dataset whose transform has jitter set) become float32 ``brightness`` / ``contrast`` tensors, each present only when some item
-    carries that factor (an item without it counts as 1).  ``sigma`` (items of a dataset whose transform has blur set) becomes the
-    float32 ``blur`` tensor, present only when some item's sigma is not 0."""
+    an int64 offset table and int32 dims; tensors are pinned by the loader (pin_memory=True).  What follows the image becomes the
+    ``flips`` / ``turn`` / ``brightness`` / ``contrast`` / ``blur`` entries of ``collate_draws``."""
     imgs = [it[0][0] for it in items]
-    flips = [it[0][1] for it in items]
-    turn = any(len(it[0]) > 2 and it[0][2] for it in items)
     ch = 3 if any(im.ndim == 3 for im in imgs) else 1
     if ch == 3:
         imgs = [im if im.ndim == 3 else np.repeat(im[:, :, None], 3, 2) for im in imgs]
@@ -706,15 +674,8 @@ def collate_rois(items):
     if len(imgs) > 1:
         offs[1:] = torch.cumsum(sizes, 0)[:-1]
     blob = torch.from_numpy(np.concatenate([np.ascontiguousarray(im).reshape(-1) for im in imgs]))
-    batch = dict(pixels=blob, offs=offs, hs=hs, ws=ws, flips=torch.tensor(flips, dtype=torch.uint8),
-                 max_h=int(hs.max()), max_w=int(ws.max()), in_channels=ch)
-    if turn:
-        batch['turn'] = True
-    for key, k in (('brightness', 3), ('contrast', 4)):
-        if any(len(it[0]) > k and it[0][k] is not None for it in items):
-            batch[key] = torch.tensor([it[0][k] if len(it[0]) > k and it[0][k] is not None else 1.0 for it in items], dtype=torch.float32)
-    if any(len(it[0]) > 5 and it[0][5] for it in items):
-        batch['blur'] = torch.tensor([it[0][5] if len(it[0]) > 5 else 0.0 for it in items], dtype=torch.float32)
+    batch = dict(pixels=blob, offs=offs, hs=hs, ws=ws, max_h=int(hs.max()), max_w=int(ws.max()), in_channels=ch)
+    batch.update(collate_draws([it[0][1:] for it in items]))
     rest = list(zip(*[it[1:] for it in items]))
     out = [batch]
     for r in rest:
@@ -733,24 +694,29 @@ def rois_to_device(batch, device, transform=None):
     return attach_draws(kw, batch, device, transform)
 
 
+def attach_settings(kw, transform):
+    """the transform's Normalize / pad settings, added to the ``load_rois`` arguments ``kw`` (``transform`` None: nothing)"""
+    if transform is not None and transform.img_norm is not None:
+        kw['mean'], kw['std'] = transform.img_norm
+    if transform is not None and getattr(transform, 'pad', None) is not None:
+        kw['pad'] = transform.pad
+    return kw
+
+
 def attach_draws(kw, batch, device, transform=None):
-    """the second half of ``rois_to_device``: the batch's flip codes and jitter factors (``batch``: a collated batch, or ``draw_items``'
-    result) and the transform's Normalize / pad settings, added to the ``load_rois`` arguments ``kw`` of ROIs already on the device"""
+    """the second half of ``rois_to_device``: the batch's flip codes, jitter factors and sigmas (``batch``: a collated batch, or
+    ``draw_items``' result) and ``attach_settings``, added to the ``load_rois`` arguments ``kw`` of ROIs already on the device"""
     if batch.get('turn') or (transform is not None and getattr(transform, 'rot90', False)):
         # the codes may hold a transpose bit: always handed over, so the kernels a run launches do not depend on the draw
         kw['flips'] = batch['flips'].to(device, non_blocking=True)
         kw['turn'] = True
     elif batch['flips'].any():
         kw['flips'] = batch['flips'].to(device, non_blocking=True)
-    if transform is not None and transform.img_norm is not None:
-        kw['mean'], kw['std'] = transform.img_norm
-    if transform is not None and getattr(transform, 'pad', None) is not None:
-        kw['pad'] = transform.pad
     if 'brightness' in batch or 'contrast' in batch:
         kw['jitter'] = tuple(batch[k].to(device, non_blocking=True) if k in batch else None for k in ('brightness', 'contrast'))
     if 'blur' in batch:
         kw['blur'] = batch['blur'].to(device, non_blocking=True)
-    return kw
+    return attach_settings(kw, transform)
 
 
 # ------------------------------------------------------------------------------------------ TRAIN --resident
@@ -860,28 +826,7 @@ class ResidentSet:
 
 
 def draw_items(transform, n):
-    """the per-item draws of n items in batch order, by the very calls ``NeustonDataset.__getitem__`` makes (``flip_code()``, then
-    ``jitter_factors()`` when jitter is set, ``blur_sigma()`` when blur is), as the ``flips`` / ``turn`` / ``brightness`` / ``contrast`` /
-    ``blur`` entries ``collate_rois`` builds
-    from such items: a ``--resident`` run and a ``--loaders 0`` run of the same command consume identical random streams."""
-    items = []
-    for _ in range(n):
-        flip = transform.flip_code() if transform is not None else 0
-        if transform is not None and getattr(transform, 'blur', None) is not None:
-            fbc = transform.jitter_factors() if getattr(transform, 'jitter', None) is not None else (None, None)
-            items.append((flip, bool(getattr(transform, 'rot90', False))) + fbc + (transform.blur_sigma(),))
-        elif transform is not None and getattr(transform, 'jitter', None) is not None:
-            items.append((flip, bool(getattr(transform, 'rot90', False))) + transform.jitter_factors())
-        elif transform is not None and getattr(transform, 'rot90', False):
-            items.append((flip, True))
-        else:
-            items.append((flip,))
-    out = dict(flips=torch.tensor([it[0] for it in items], dtype=torch.uint8))
-    if any(len(it) > 1 and it[1] for it in items):
-        out['turn'] = True
-    for key, k in (('brightness', 2), ('contrast', 3)):
-        if any(len(it) > k and it[k] is not None for it in items):
-            out[key] = torch.tensor([it[k] if len(it) > k and it[k] is not None else 1.0 for it in items], dtype=torch.float32)
-    if any(len(it) > 4 and it[4] for it in items):
-        out['blur'] = torch.tensor([it[4] if len(it) > 4 else 0.0 for it in items], dtype=torch.float32)
-    return out
+    """the per-item draws of n items in batch order, by the very call ``NeustonDataset.__getitem__`` makes (``RoiTransform.draw_item``),
+    as the entries ``collate_rois`` builds from such items (``collate_draws``): a ``--resident`` run and a ``--loaders 0`` run of the
+    same command consume identical random streams."""
+    return collate_draws([transform.draw_item() if transform is not None else (0,) for _ in range(n)])

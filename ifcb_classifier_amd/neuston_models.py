@@ -470,12 +470,11 @@ class NeustonModel(nn.Module):
         self._teacher_ready = False
 
     # TRAINING (fast path: one fused HIP program; loss accumulated on device, read once per epoch) #
-    def fit_batch(self, input_data, input_classes):
+    def _load_fit_batch(self, input_data, input_classes):
+        """what ``fit_batch`` and ``fit_batch_ddp`` do ahead of the step, on the current slot and stream: load the batch, copy its
+        targets, mix it (``batch_mix``) and, with a teacher attached, load and run the teacher -> N"""
         eng = self.model.engine
-        if torch.is_tensor(input_data):
-            N = eng.load_input_nchw(input_data)
-        else:
-            N = eng.load_rois(**input_data)
+        N = eng.load_input_nchw(input_data) if torch.is_tensor(input_data) else eng.load_rois(**input_data)
         eng.target[:N].copy_(input_classes, non_blocking=True)
         if self.batch_mix is not None:
             self._mix_loaded(self.batch_mix, N)
@@ -483,7 +482,11 @@ class NeustonModel(nn.Module):
             self._load_teacher_batch(input_data)
             self._run_teacher(N)
         self.model.train()
-        eng.train_step(N)
+        return N
+
+    def fit_batch(self, input_data, input_classes):
+        N = self._load_fit_batch(input_data, input_classes)
+        self.model.engine.train_step(N)
         return N
 
     # ---- pipelined form of the three batch calls: the NEXT batch is uploaded and preprocessed on a side stream into the
@@ -554,17 +557,14 @@ class NeustonModel(nn.Module):
     def stage_resident(self, res, i0, i1, transform=None):
         """stage ROIs i0..i1-1 of a bin whose .roi blob and ADC table already live on the device (``res`` from
         ``upload_bin``): the preprocess kernel reads them where they are -- no per-batch slicing, concatenation or upload"""
+        from .neuston_data import attach_settings
         eng = self.model.engine
         slot, side = eng.prefetch_begin()
         with torch.cuda.stream(side):
             side.wait_event(res['ready'])
             kw = dict(pixels=res['pixels'], offs=res['offs'][i0:i1], hs=res['hs'][i0:i1], ws=res['ws'][i0:i1],
                       max_h=res['max_h'], max_w=res['max_w'], in_channels=1)
-            if transform is not None and transform.img_norm is not None:
-                kw['mean'], kw['std'] = transform.img_norm
-            if transform is not None and getattr(transform, 'pad', None) is not None:
-                kw['pad'] = transform.pad
-            n = eng.load_rois(slot=slot, **kw)
+            n = eng.load_rois(slot=slot, **attach_settings(kw, transform))
         eng.prefetch_end(slot)
         return n
 
@@ -640,16 +640,8 @@ class NeustonModel(nn.Module):
     def fit_batch_ddp(self, input_data, input_classes, world, all_reduce):
         """data-parallel twin of fit_batch: per-rank local BatchNorm statistics (no SyncBN upstream), gradient
         all-reduce over RCCL launched per finished bucket and overlapped with the rest of backward."""
-        eng = self.model.engine
-        N = eng.load_input_nchw(input_data) if torch.is_tensor(input_data) else eng.load_rois(**input_data)
-        eng.target[:N].copy_(input_classes, non_blocking=True)
-        if self.batch_mix is not None:
-            self._mix_loaded(self.batch_mix, N)
-        if self._need_teacher():
-            self._load_teacher_batch(input_data)
-            self._run_teacher(N)
-        self.model.train()
-        eng.train_step_ddp(N, world, all_reduce)
+        N = self._load_fit_batch(input_data, input_classes)
+        self.model.engine.train_step_ddp(N, world, all_reduce)
         return N
 
     def eval_batch(self, input_data, input_classes=None):

@@ -101,16 +101,11 @@ def gpu_moments(loader, resize, device=0, pad=None):
     dev = torch.device('cuda', device)
     torch.cuda.set_device(dev)
     ctx = _lib.Context(device)
-    d = _lib.RoiDesc()
-    d.S, d.out_channels, d.flip_bits_valid, d.dtype = resize, 8, 0, _lib.BF16
-    for k in range(3):
-        d.mean[k], d.std[k], d.tin_scale[k], d.tin_shift[k] = 0.0, 1.0, 1.0, 0.0
     try:
         for batch in loader:
             kw = rois_to_device(batch[0], dev)
             n, ch = int(kw['hs'].numel()), int(kw['in_channels'])
-            d.n_img, d.in_channels = n, ch
-            fn, fill = ('ifcbk_roi_preprocess', ()) if pad is None else ('ifcbk_roi_preprocess_fit', (_lib.pad_fill(pad),))
+            d, fn, fill = _lib.roi_resize(n, resize, ch, _lib.BF16, pad=pad)
             need = getattr(ctx.lib, fn + '_workspace')(C.byref(d), kw['max_h'], kw['max_w'])
             if need > ctx.lib.ifcbk_ctx_workspace_bytes(ctx.h):
                 ctx.reserve(need)

@@ -271,12 +271,13 @@ def _stub(radius, kind):
     ctx, pre = _Calls(), _Calls()
     loads = []
 
-    def load_into(c, stream, slot, main, *a):
+    def load_into(target, *a, **kw):
+        c, stream, tstream, slot, main = target
         loads.append((c, slot, main) + a)
-        return a[2].numel()
-    s = types.SimpleNamespace(ctx=ctx, pre_ctx=pre, pre_stream=types.SimpleNamespace(cuda_stream=77), stream=lambda: 11, in_slot=0,
+    s = types.SimpleNamespace(ctx=ctx, pre_ctx=pre, pre_stream=types.SimpleNamespace(cuda_stream=77), in_slot=0,
                               in_kind=[kind, kind], in_u8=['u8_0', 'u8_1'], in_bufs=['d_0', 'd_1'], cdtype=_lib.BF16, blur_radius=radius,
-                              net=types.SimpleNamespace(S=299), _load_rois_into=load_into)
+                              net=types.SimpleNamespace(S=299), _load_rois_into=load_into, dev=None)
+    s._slot_target, s._slot_image = types.MethodType(Engine._slot_target, s), types.MethodType(Engine._slot_image, s)
     return s, ctx, pre, loads
 
 
@@ -284,7 +285,8 @@ def test_load_rois_launches_nothing_more_without_sigmas_and_one_call_with_them()
     px = torch.zeros(12, dtype=torch.uint8)
     tabs = (torch.zeros(3, dtype=torch.int64), torch.full((3,), 2, dtype=torch.int32), torch.full((3,), 2, dtype=torch.int32))
     sig = torch.tensor([0.0, 1.0, 2.0])
-    with mock.patch('ifcb_classifier_amd.engine._vp', lambda t: t):
+    with mock.patch('ifcb_classifier_amd.engine._vp', lambda t: t), \
+            mock.patch('torch.cuda.current_stream', lambda dev: types.SimpleNamespace(cuda_stream=11)):
         for more in (dict(), dict(blur=None)):
             for radius in (None, 6):
                 s, ctx, pre, loads = _stub(radius, 'u8')
@@ -293,7 +295,8 @@ def test_load_rois_launches_nothing_more_without_sigmas_and_one_call_with_them()
         # the current slot: behind the resize, on its ctx and stream, on the buffer the resize wrote
         s, ctx, pre, loads = _stub(6, 'u8')
         assert Engine.load_rois(s, px, *tabs, 2, 2, blur=sig) == 3
-        assert len(loads) == 1 and not pre.calls and ctx.calls == [('ifcbk_batch_blur', 'u8_0', _lib.MIX_U8, 3, 299, sig, 6, 11)]
+        (c,) = ctx.calls
+        assert len(loads) == 1 and not pre.calls and c[:7] == ('ifcbk_batch_blur', 'u8_0', _lib.MIX_U8, 3, 299, sig, 6) and c[7].value == 11
         # a prefetch slot: the prefetch ctx and stream, the dense tensor of that slot
         s, ctx, pre, loads = _stub(12, 'nhwc')
         assert Engine.load_rois(s, px, *tabs, 2, 2, slot=1, blur=sig) == 3
