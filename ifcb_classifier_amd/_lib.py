@@ -160,6 +160,7 @@ _PROTOS = {
     'ifcbk_grad_clip_state_floats': (_sz, []),
     'ifcbk_grad_norm': (_i, [_vp, _vp, C.c_int64, _f, _f, _vp, _vp]),
     'ifcbk_adam_clip_flat': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _f, _f, _f, _f, _f, _i, _f, _f, _f, _vp, _vp]),
+    'ifcbk_adamw_flat': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _f, _f, _f, _f, _f, _i, _f, _f, _f, _vp, _vp]),
     'ifcbk_sgd_clip_flat': (_i, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _f, _f, _f, _f, _f, _f, _vp, _vp]),
     'ifcbk_roi_preprocess': (_i, [_vp, C.POINTER(RoiDesc), _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     'ifcbk_roi_preprocess_workspace': (_sz, [C.POINTER(RoiDesc), _i, _i]),

@@ -15,7 +15,7 @@ enum {  // IFCBK_OP_SOFTMAX_XENT and IFCBK_OP_SOFTMAX_XENT_W
 };
 enum {  // IFCBK_OP_ADAM
     ADAM_P, ADAM_G, ADAM_M, ADAM_V, ADAM_E, ADAM_CLIP_STATE,                                                       // p[]
-    ADAM_N = 0, ADAM_STEP,                                                                                         // i[]
+    ADAM_N = 0, ADAM_STEP, ADAM_DECOUPLED,                                                                         // i[]
     ADAM_LR = 0, ADAM_BETA1, ADAM_BETA2, ADAM_EPS, ADAM_WEIGHT_DECAY, ADAM_GRAD_SCALE, ADAM_EMA_W, ADAM_MAX_NORM   // f[]
 };
 enum {  // IFCBK_OP_SGD
@@ -176,6 +176,12 @@ static int run_loss(ifcbk_ctx* c, const ifcbk_op* o, void* st) {
 static int run_one(ifcbk_ctx* c, const ifcbk_op* o, void* st) {
     void* const* p = o->p;
     const int acc = o->flags & 1, pacc = (o->flags >> 1) & 1;
+    // the Adam op in its decoupled form (i[2] != 0, TRAIN --optimizer AdamW): the same operands, handed to the other typed call
+    if (o->kind == IFCBK_OP_ADAM && o->i[ADAM_DECOUPLED])
+        return ifcbk_adamw_flat(c, (float*)p[ADAM_P], (const float*)p[ADAM_G], (float*)p[ADAM_M], (float*)p[ADAM_V], (float*)p[ADAM_E],
+                                o->i[ADAM_N], o->f[ADAM_LR], o->f[ADAM_BETA1], o->f[ADAM_BETA2], o->f[ADAM_EPS], o->f[ADAM_WEIGHT_DECAY],
+                                (int)o->i[ADAM_STEP], o->f[ADAM_GRAD_SCALE], o->f[ADAM_EMA_W], o->f[ADAM_MAX_NORM],
+                                (float*)p[ADAM_CLIP_STATE], st);
     switch (o->kind) {
         case IFCBK_OP_CONV_FWD: return ifcbk_conv2d_fwd(c, &o->u.conv, p[0], p[1], p[2], (float*)p[3], st);
         case IFCBK_OP_CONV_FWD_AFFINE:
@@ -677,7 +683,8 @@ extern "C" int ifcbk_op_kernel(const ifcbk_op* o, char* name, size_t cap) {
         case IFCBK_OP_MAXPOOL_BWD: snprintf(name, cap, "maxpool_bwd_kernel"); break;
         case IFCBK_OP_AVGPOOL_FWD: case IFCBK_OP_AVGPOOL_AFFINE: snprintf(name, cap, "avgpool_fwd_kernel"); break;
         case IFCBK_OP_AVGPOOL_BWD: snprintf(name, cap, "avgpool_bwd_kernel"); break;
-        case IFCBK_OP_ADAM: snprintf(name, cap, "adam_kernel"); break;
+        // (the decoupled instantiation by the name a profile lists; a decoupled op without decay runs the plain one: ifcbk_adamw_flat)
+        case IFCBK_OP_ADAM: snprintf(name, cap, o->i[ADAM_DECOUPLED] && o->f[ADAM_WEIGHT_DECAY] != 0.f ? "adam_kernel<true>" : "adam_kernel"); break;
         case IFCBK_OP_SGD: snprintf(name, cap, "sgd_kernel"); break;
         case IFCBK_OP_BIAS_RELU_BWD: snprintf(name, cap, "bias_relu_bwd_kernel"); break;
         case IFCBK_OP_DROPOUT: snprintf(name, cap, "dropout_apply_kernel"); break;
@@ -752,7 +759,8 @@ extern "C" int ifcbk_op_cost(const ifcbk_op* o, double* flops, double* bytes) {
             by = (double)d.N * d.HW * d.C * 2;
             break;
         }
-        // (+ the weight average: read and written; + the norm's pass over the gradient when the op clips)
+        // (+ the weight average: read and written; + the norm's pass over the gradient when the op clips; the decoupled form moves the
+        //  same bytes)
         case IFCBK_OP_ADAM: by = (double)o->i[ADAM_N] * (28 + (o->p[ADAM_E] ? 8 : 0) + (o->p[ADAM_CLIP_STATE] ? 4 : 0)); break;
         case IFCBK_OP_SGD: by = (double)o->i[SGD_N] * ((o->p[SGD_M] ? 20 : 12) + (o->p[SGD_E] ? 8 : 0) + (o->p[SGD_CLIP_STATE] ? 4 : 0)); break;
         case IFCBK_OP_SOFTMAX_XENT: case IFCBK_OP_SOFTMAX_XENT_W: {

@@ -594,6 +594,11 @@ __global__ void softmax_kernel(const float* logits, int N, int NC, float* probs)
 }
 
 // ---------------------------------------------------------------- optimizers (flat)
+// One kernel, two forms.  DECOUPLED = false is torch.optim.Adam: wd is the L2 coefficient, gr = g * gscale + wd * p.  DECOUPLED = true is
+// torch.optim.AdamW (ifcbk_adamw_flat): wd is the decay FACTOR fl(1 - lr * weight_decay) the host formed, p is scaled by it first (one
+// fp32 product) and the gradient carries no wd * p term.  A template parameter, not an argument: the L2 form's code is what it was
+// before the other one existed (a run-time branch could change how g * gscale + wd * p contracts)
+template <bool DECOUPLED>
 __global__ __launch_bounds__(256) void adam_kernel(float* p, const float* g, float* m, float* v, int64_t n, float lr,
                                                    float b1, float b2, float eps, float wd, float bc1, float sbc2,
                                                    float gscale, float* ema, float ew, const float* clip) {
@@ -609,7 +614,13 @@ __global__ __launch_bounds__(256) void adam_kernel(float* p, const float* g, flo
         float* P = &pp.x; float* G = &gg.x; float* Mm = &mm.x; float* V = &vv.x;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            float gr = G[j] * gscale + wd * P[j];
+            float gr;
+            if (DECOUPLED) {
+                P[j] *= wd;
+                gr = G[j] * gscale;
+            } else {
+                gr = G[j] * gscale + wd * P[j];
+            }
             Mm[j] = b1 * Mm[j] + (1.f - b1) * gr;
             V[j] = b2 * V[j] + (1.f - b2) * gr * gr;
             float denom = sqrtf(V[j]) / sbc2 + eps;
@@ -627,11 +638,17 @@ __global__ __launch_bounds__(256) void adam_kernel(float* p, const float* g, flo
         }
     } else {
         for (int64_t k = i; k < n; ++k) {
-            float gr = g[k] * gscale + wd * p[k];
+            float gr = DECOUPLED ? g[k] * gscale : g[k] * gscale + wd * p[k];
             m[k] = b1 * m[k] + (1.f - b1) * gr;
             v[k] = b2 * v[k] + (1.f - b2) * gr * gr;
             float denom = sqrtf(v[k]) / sbc2 + eps;
-            float pn = p[k] - (lr / bc1) * (m[k] / denom);
+            float pn;
+            if (DECOUPLED) {
+                const float pk = p[k] * wd;                       // (a statement of its own: the product is rounded, as P[j] *= wd is)
+                pn = pk - (lr / bc1) * (m[k] / denom);
+            } else {
+                pn = p[k] - (lr / bc1) * (m[k] / denom);
+            }
             p[k] = pn;
             if (ema) ema[k] = ema[k] + ew * (pn - ema[k]);
         }
@@ -859,7 +876,7 @@ extern "C" int ifcbk_adam_clip_flat(ifcbk_ctx* ctx, float* p, const float* g, fl
     }
     float bc1 = 1.f - powf(beta1, (float)step);
     float sbc2 = sqrtf(1.f - powf(beta2, (float)step));
-    hipLaunchKernelGGL(adam_kernel, dim3(cdiv(cdiv(n, 4), 256)), dim3(256), 0, ST, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, sbc2, grad_scale, ema, ema_w, (const float*)clip_state);
+    hipLaunchKernelGGL(adam_kernel<false>, dim3(cdiv(cdiv(n, 4), 256)), dim3(256), 0, ST, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, sbc2, grad_scale, ema, ema_w, (const float*)clip_state);
     IFCBK_LAUNCH_CHECK(ctx, "adam");
     return 0;
 }
@@ -871,6 +888,31 @@ extern "C" int ifcbk_adam_ema_flat(ifcbk_ctx* ctx, float* p, const float* g, flo
 extern "C" int ifcbk_adam_flat(ifcbk_ctx* ctx, float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1,
                                float beta2, float eps, float weight_decay, int step, float grad_scale, void* stream) {
     return ifcbk_adam_clip_flat(ctx, p, g, m, v, nullptr, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, 0.f, 0.f, nullptr, stream);
+}
+// torch.optim.AdamW: the decoupled decay p *= 1 - lr * weight_decay ahead of Adam's update, which then carries no wd * p term.  The
+// factor is formed here, in double from the two fp32 scalars, and rounded once; clipping scales the gradient only.  weight_decay == 0
+// is ifcbk_adam_clip_flat (it is that call: bit for bit)
+extern "C" int ifcbk_adamw_flat(ifcbk_ctx* ctx, float* p, const float* g, float* m, float* v, float* ema, int64_t n, float lr,
+                                float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale, float ema_w,
+                                float max_norm, float* clip_state, void* stream) {
+    if (!(weight_decay >= 0.f) || isinf(weight_decay))
+        IFCBK_FAIL(ctx, IFCBK_EINVAL, "adamw: weight_decay %g is not a finite number >= 0", (double)weight_decay);
+    if (weight_decay == 0.f)
+        return ifcbk_adam_clip_flat(ctx, p, g, m, v, ema, n, lr, beta1, beta2, eps, 0.f, step, grad_scale, ema_w, max_norm, clip_state, stream);
+    if (step < 1) IFCBK_FAIL(ctx, IFCBK_EINVAL, "adamw: step must be >= 1");
+    if (ema && !ema_w_ok(ema_w)) IFCBK_FAIL(ctx, IFCBK_EINVAL, "adamw: ema_w %g outside [0, 1]", (double)ema_w);
+    if (ema && ((uintptr_t)ema & 15) != ((uintptr_t)p & 15)) IFCBK_FAIL(ctx, IFCBK_EINVAL, "adamw: ema must be aligned as p is");
+    if (ema_w == 0.f) ema = nullptr;
+    if (clip_state) {
+        const int rc = ifcbk_grad_norm(ctx, g, n, grad_scale, max_norm, clip_state, stream);
+        if (rc) return rc;
+    }
+    const float decay = (float)(1.0 - (double)lr * (double)weight_decay);
+    float bc1 = 1.f - powf(beta1, (float)step);
+    float sbc2 = sqrtf(1.f - powf(beta2, (float)step));
+    hipLaunchKernelGGL((adam_kernel<true>), dim3(cdiv(cdiv(n, 4), 256)), dim3(256), 0, ST, p, g, m, v, n, lr, beta1, beta2, eps, decay, bc1, sbc2, grad_scale, ema, ema_w, (const float*)clip_state);
+    IFCBK_LAUNCH_CHECK(ctx, "adamw");
+    return 0;
 }
 extern "C" int ifcbk_sgd_clip_flat(ifcbk_ctx* ctx, float* p, const float* g, float* mom, float* ema, int64_t n, float lr, float momentum,
                                    float weight_decay, float grad_scale, float ema_w, float max_norm, float* clip_state, void* stream) {

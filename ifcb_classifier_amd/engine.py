@@ -98,7 +98,7 @@ class Engine:
     def __init__(self, net, device=0, max_batch=32, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, dtype='bf16', optimizer='adam',
                  momentum=0.0, plan_only=False, train_batch=None, dp_world=None, class_weights=None, weight_decay=0.0,
                  label_smoothing=0.0, focal_gamma=0.0, mix=False, ema_decay=None, ema_warmup=True, distill=None, clip_grad=None,
-                 blur_radius=None):
+                 blur_radius=None, lr_schedule=None):
         # dp_world: world size of the data-parallel job this replica belongs to (None: WORLD_SIZE of the launcher, else an
         # initialised torch.distributed group, else 1) -- it picks the program-lane default, and train_step_ddp checks it
         self._dp_world_arg = None if dp_world is None else int(dp_world)
@@ -107,12 +107,20 @@ class Engine:
         self.plan_only = bool(plan_only)
         if not self.plan_only and not torch.cuda.is_available():
             raise RuntimeError('ifcb_classifier_amd needs a HIP device (MI355X); none is visible and there is no CPU path')
-        if str(optimizer).lower() not in ('adam', 'sgd'):
-            raise ValueError("optimizer must be 'adam' (the reference's only behaviour, neuston_models.py:63-64) or 'sgd'")
+        if str(optimizer).lower() not in ('adam', 'sgd', 'adamw'):
+            raise ValueError("optimizer must be 'adam' (the reference's only behaviour, neuston_models.py:63-64), 'sgd' or 'adamw'")
+        # 'adamw' (additive, TRAIN --optimizer AdamW): Adam's op, buffers, step count and bias correction with the op's `decoupled` operand
+        # set, so that weight_decay is torch.optim.AdamW's p *= 1 - lr * wd instead of the L2 term
         self.optimizer, self.momentum = str(optimizer).lower(), float(momentum)
         # the slots _set_update stamps on every step, resolved once
         opt_kind = _lib.OP_SGD if self.optimizer == 'sgd' else _lib.OP_ADAM
-        self._upd_step, self._upd_scale, self._upd_ema_w = (ops.slot(opt_kind, name) for name in ('step', 'grad_scale', 'ema_w'))
+        self._upd_step, self._upd_scale, self._upd_ema_w, self._upd_lr = (ops.slot(opt_kind, name)
+                                                                          for name in ('step', 'grad_scale', 'ema_w', 'lr'))
+        # additive (TRAIN --lr-schedule / --warmup): an lr_schedule.LrSchedule (anything with .at(t)); the optimizer ops of step t + 1 then
+        # carry fp32(at(t)) in their lr operand.  None: the ops keep the lr written at plan time
+        if lr_schedule is not None and not callable(getattr(lr_schedule, 'at', None)):
+            raise ValueError('lr_schedule must be None or an object with .at(step index) -> rate (lr_schedule.LrSchedule)')
+        self.lr_schedule = lr_schedule
         # additive options (TRAIN --weight-decay / --class-norm; upstream has neither): torch's L2 form g + wd * p in the fused
         # Adam / SGD kernels, and per-class weights of the loss (nn.CrossEntropyLoss(weight=...)); None / 0.0: upstream's behaviour
         self.weight_decay = float(weight_decay or 0.0)
@@ -1187,12 +1195,22 @@ class Engine:
         self.run(self.plan(N).bwd)
 
     def _set_update(self, op, grad_scale=1.0):
-        """per-step scalars of the optimizer op: the step count (Adam's bias correction), the gradient scale (1/world) and, with a
-        weight average, the weight of this step's update (_ema_begin_step)"""
+        """per-step scalars of the optimizer op: the step count (Adam's bias correction), the gradient scale (1/world), with a weight
+        average the weight of this step's update (_ema_begin_step), and with a schedule this step's learning rate: a function of the
+        step count alone, so every way of launching a step, at any batch size and after any load, carries the same rate"""
         op.i[self._upd_step] = self.step_count
         op.f[self._upd_scale] = grad_scale
+        if self.lr_schedule is not None:
+            op.f[self._upd_lr] = self.lr_schedule.at(self.step_count - 1)
         if self.ema_decay is not None:
             op.f[self._upd_ema_w] = self._ema_w
+
+    @property
+    def lr_now(self):
+        """the learning rate of the last optimizer step as the op carried it (ahead of the first: of the first); ``lr`` stays the base"""
+        if self.lr_schedule is None:
+            return self.lr
+        return C.c_float(self.lr_schedule.at(max(self.step_count, 1) - 1)).value
 
     def adam_step(self, N):
         pl = self.plan(N)

@@ -367,8 +367,26 @@ class NeustonModel(nn.Module):
         if eng.optimizer == 'sgd':            # additive option; the reference's only behaviour is Adam(lr=0.001) (:63-64)
             from torch.optim import SGD
             return SGD(self.parameters(), lr=eng.lr, momentum=eng.momentum, weight_decay=eng.weight_decay)
+        if eng.optimizer == 'adamw':          # additive option: decoupled weight decay, every parameter decayed
+            from torch.optim import AdamW
+            return AdamW(self.parameters(), lr=eng.lr, betas=tuple(eng.betas), eps=eng.eps, weight_decay=eng.weight_decay)
         from torch.optim import Adam
         return Adam(self.parameters(), lr=eng.lr, weight_decay=eng.weight_decay)
+
+    def set_lr_schedule(self, steps_per_epoch):
+        """TRAIN --lr-schedule / --warmup / --lr-min: hand the engine the run's schedule, T = emax * steps_per_epoch updates of which
+        W = round(warmup * steps_per_epoch) warm up (``steps_per_epoch``: the per-rank length of the training loader, the same on every
+        rank).  Without any of the three flags nothing is set and the engine keeps its one rate.  -> the schedule or None"""
+        from .lr_schedule import LrSchedule, schedule_steps
+        hp = self.hparams
+        kind = getattr(hp, 'lr_schedule', None) or 'constant'
+        warmup = float(getattr(hp, 'warmup', None) or 0.0)
+        if kind == 'constant' and not warmup:
+            return None
+        eng = self.model.engine
+        T, W = schedule_steps(hp.emax, warmup, steps_per_epoch)
+        eng.lr_schedule = LrSchedule(kind, eng.lr, T, W, float(getattr(hp, 'lr_min', None) or 0.0))
+        return eng.lr_schedule
 
     def load_state_dict(self, state_dict, strict=True):
         """``criterion.weight`` (the buffer of a weighted nn.CrossEntropyLoss, TRAIN --class-norm) is derived from the hyper-parameters:
@@ -703,11 +721,19 @@ class NeustonModel(nn.Module):
         eoe = 'Best Epoch: {}, train_loss: {:.3f}, val_loss: {:.3f}, val_f1_w={:02.1f}%, val_f1_m={:02.1f}%'
         eoe = eoe.format(True if self.current_epoch == self.best_epoch else self.best_epoch + 1, self.agg_train_loss,
                          validation_loss, 100 * f1_weighted, 100 * f1_macro)
+        # TRAIN --lr-schedule / --warmup: the rate of the epoch's last step joins the line and the logged scalars (epochs.csv); without a
+        # schedule both are what they were
+        eng = self.model.engine
+        lr = eng.lr_now if getattr(eng, 'lr_schedule', None) is not None else None
+        if lr is not None:
+            eoe += ', lr: {:.4g}'.format(lr)
         print(eoe, flush=True, end='\n\n')
         self.logged = dict(epoch=self.current_epoch, best=self.best_epoch == self.current_epoch,
                            train_loss=self.agg_train_loss, val_loss=validation_loss.item(),
                            input_classes=input_classes, output_classes=output_classes, input_srcs=input_srcs,
                            outputs=outputs, f1_macro=f1_macro, f1_weighted=f1_weighted)
+        if lr is not None:
+            self.logged['lr'] = lr
         self.agg_train_loss = 0.0
         return dict(hiddens=dict(outputs=outputs))
 
@@ -760,6 +786,9 @@ class NeustonModel(nn.Module):
             group = dict(lr=eng.lr, momentum=eng.momentum, dampening=0, weight_decay=eng.weight_decay or 0, nesterov=False, params=ids)
         else:
             group = dict(lr=eng.lr, betas=tuple(eng.betas), eps=eng.eps, weight_decay=eng.weight_decay or 0, amsgrad=False, params=ids)
+        if eng.lr_schedule is not None:
+            # as a torch scheduler leaves its optimizer's groups: lr is the rate of the last step taken, initial_lr the base
+            group.update(lr=eng.lr_now, initial_lr=eng.lr)
         return dict(state=state, param_groups=[group])
 
     def checkpoint_dict(self, epoch=0, global_step=0):

@@ -104,6 +104,26 @@ def _clip_grad(text):
     return v
 
 
+def _lr_nonneg(text):
+    v = float(text)
+    if not 0.0 <= v < float('inf'):            # (nan fails both comparisons)
+        raise argparse.ArgumentTypeError('must be finite and not negative, got %r' % text)
+    return v
+
+
+def check_lr_flags(args):
+    """the combinations of --lr-schedule / --warmup / --lr-min / --learning-rate / --emax that TRAIN refuses, each with its message"""
+    kind, warmup, lr_min = args.lr_schedule, args.warmup, args.lr_min
+    if lr_min > args.learning_rate:
+        raise SystemExit('TRAIN --lr-min {:g} is above --learning-rate {:g}: the rate decays from the latter to the former'.format(
+            lr_min, args.learning_rate))
+    if warmup and warmup >= args.emax:
+        raise SystemExit('TRAIN --warmup {:g} must be less than --emax {}: the warm-up would take the whole run'.format(warmup, args.emax))
+    if kind == 'constant' and lr_min:
+        raise SystemExit('TRAIN --lr-min {:g} needs a decaying --lr-schedule (cosine or linear): a constant rate never gets there '
+                         '(--warmup alone into a constant rate is fine)'.format(lr_min))
+
+
 class _ExclusiveLossScalar(argparse.Action):
     """stores --label-smoothing / --focal-gamma (and --mixup / --cutmix / --distill); the second of the two to arrive non-zero is an
     argparse error naming both, as is --focal-gamma, --mixup or --cutmix beside --distill"""
@@ -441,6 +461,7 @@ def do_training(args):
         args.result_files = ['results.mat training_image_basenames training_classes image_basenames input_classes '
                              'output_scores confusion_matrix counts_perclass f1_perclass f1_weighted f1_macro'.split()]
     callbacks = [SaveValidationResults(outdir=args.outdir, outfile=rf[0], series=rf[1:]) for rf in args.result_files]
+    check_lr_flags(args)
     args.seed = seed_everything(args.seed or None)
     if getattr(args, 'blur', None) is None:
         # unset: the model file and args.yml carry no blur entry at all
@@ -516,6 +537,11 @@ def do_training(args):
         raise ValueError('--batch %d: one launch addresses each tensor through a 2 GiB buffer descriptor, which holds %d images '
                          'of %s; use --batch <= %d per GPU (and more GPUs for a larger global batch)'
                          % (args.batch_size, eng.window_batch, args.MODEL, eng.window_batch))
+    # --lr-schedule / --warmup: the per-rank length of the training loader (--resident: the same length) times --emax is the run
+    sched = classifier.set_lr_schedule(len(training_loader))
+    if sched is not None:
+        print('Learning rate: {} schedule over {} steps, {} of them warm-up, from {:g} to {:g}'.format(
+            sched.kind, sched.total_steps, sched.warmup_steps, sched.base, sched.base if sched.kind == 'constant' else sched.lr_min))
     trainer.fit(classifier, training_loader, validation_loader)
     if rank != 0:
         return
@@ -762,10 +788,13 @@ def argparse_nn_train(train_subparser):
     out.add_argument('--onnx', action='store_true', help='Additionally output an onnx version of the model')
     out.add_argument('--results', dest='result_files', metavar=('FNAME', 'SERIES'), nargs='+', action='append', help='FNAME: validation-results filename or pattern ("{epoch}"); .json .h5 .mat.  SERIES: data to include.')
     optim = t.add_argument_group(title='Optimization', description='(MI355X path, additive: upstream keeps these flags commented out, neuston_net.py:385-390; the defaults are its only behaviour, Adam(lr=0.001))')
-    optim.add_argument('--optimizer', default='Adam', choices=['Adam', 'SGD'], help='Select an optimizer. Default is Adam')
+    optim.add_argument('--optimizer', default='Adam', choices=['Adam', 'SGD', 'AdamW'], help='Select an optimizer. AdamW (MI355X path, additive) is Adam with decoupled weight decay, as torch.optim.AdamW over all parameters: --weight-decay WD then shrinks every parameter by the factor 1 - lr * WD ahead of each step instead of joining the gradient, and follows the --lr-schedule. Default is Adam')
     optim.add_argument('--learning-rate', default=0.001, type=float, help='Set a learning rate. Default is 0.001')
+    optim.add_argument('--lr-schedule', choices=['constant', 'cosine', 'linear'], default='constant', help='(MI355X path, additive) How the learning rate moves over the run\'s emax * (batches per epoch) optimizer steps, behind any --warmup: "cosine" decays from --learning-rate to --lr-min along half a cosine (torch\'s CosineAnnealingLR, stepped per batch), "linear" along a straight line; the rate is a launch argument of the fused optimizer step. Early stopping ends the run part-way down the curve. Each epoch then reports the rate of its last step. Default is constant')
+    optim.add_argument('--warmup', metavar='EPOCHS', type=_lr_nonneg, default=0.0, help='(MI355X path, additive) Linear warm-up: over the first EPOCHS epochs (a float, e.g. 0.5; rounded to whole steps) the rate rises from --learning-rate / W to --learning-rate, W the number of warm-up steps, as torch\'s LinearLR. Must be less than --emax; combines with every --lr-schedule. Default is 0 (none)')
+    optim.add_argument('--lr-min', metavar='LR', type=_lr_nonneg, default=0.0, help='(MI355X path, additive) The rate a cosine or linear --lr-schedule ends at. A float in [0, --learning-rate]. Default is 0')
     optim.add_argument('--momentum', default=0.0, type=float, help='SGD momentum. Default is 0')
-    optim.add_argument('--weight-decay', default=0.0, type=float, help='L2 weight decay of every parameter, as torch.optim.Adam/SGD(weight_decay=WD) (not AdamW). Default is 0')
+    optim.add_argument('--weight-decay', default=0.0, type=float, help='L2 weight decay of every parameter, as torch.optim.Adam/SGD(weight_decay=WD); with "--optimizer AdamW" the decoupled decay of torch.optim.AdamW(weight_decay=WD). Default is 0')
     optim.add_argument('--class-norm', metavar='POWER', nargs='?', const=1.0, type=_class_norm_power, default=None, help='Bias results to emphasize smaller classes: weight the loss of class c by n_c^-POWER (n_c: training images of the class), scaled to a mean weight of 1 per training image. POWER defaults to 1 ("balanced"); 0 weights all classes equally. Default (unset) is the unweighted loss')
     optim.add_argument('--label-smoothing', metavar='EPS', default=0.0, type=_label_smoothing, action=_ExclusiveLossScalar, help='Label smoothing of the loss, as nn.CrossEntropyLoss(label_smoothing=EPS): the target distribution is (1-EPS) one-hot + EPS/C uniform, for noisy annotations. A float in [0, 1]; val_loss follows the smoothed value. Default is 0 (hard labels)')
     optim.add_argument('--focal-gamma', metavar='GAMMA', default=0.0, type=_focal_gamma, action=_ExclusiveLossScalar, help='Focal loss against class imbalance: the loss of an image is scaled by (1 - p)^GAMMA, p the softmax probability of its class, so images the network already classifies confidently count less. A finite float >= 0; composes with --class-norm (its weights are the per-class alpha), not with --label-smoothing; val_loss follows the focal value. Default is 0 (cross-entropy)')

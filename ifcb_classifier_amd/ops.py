@@ -64,7 +64,7 @@ OPERANDS = {
     L.OP_SOFTMAX: _row('logits probs', 'N NC'),
     L.OP_SOFTMAX_XENT: _LOSS,                                              # (class_weight stays NULL: the plain kind does not read it)
     L.OP_SOFTMAX_XENT_W: _LOSS,
-    L.OP_ADAM: _row('P G M V E clip_state', 'n step', 'lr beta1 beta2 eps weight_decay grad_scale ema_w max_norm'),
+    L.OP_ADAM: _row('P G M V E clip_state', 'n step decoupled', 'lr beta1 beta2 eps weight_decay grad_scale ema_w max_norm'),
     L.OP_SGD: _row('P G M E clip_state', 'n step', 'lr momentum weight_decay grad_scale ema_w max_norm'),
     L.OP_STEP_COUNTERS: _row('num_batches_tracked loss_sum loss', 'n'),
 }

@@ -789,7 +789,7 @@ class PlanBuilder:
 
     def _optimizer_op(self):
         e, opt = self.e, OpList()
-        # step, grad_scale and ema_w are stamped per step (Engine._set_update)
+        # step, grad_scale and ema_w are stamped per step (Engine._set_update), and with a schedule lr
         p, f = dict(P=_vp(e.P), G=_vp(e.G)), dict(lr=e.lr, weight_decay=e.weight_decay, grad_scale=1.0)
         if e.ema_decay is not None:                      # TRAIN --ema: E at the offset of P (every bucket's op carries its slice)
             p['E'] = _vp(e.E)
@@ -800,7 +800,9 @@ class PlanBuilder:
             opt.add(_lib.OP_SGD, 'sgd', p=dict(p, M=_vp(e.M) if e.momentum else None), i=dict(n=e.nparam_padded, step=1),
                     f=dict(f, momentum=e.momentum))
         else:
-            opt.add(_lib.OP_ADAM, 'adam', p=dict(p, M=_vp(e.M), V=_vp(e.V)), i=dict(n=e.nparam_padded, step=1),
+            # additive option (TRAIN --optimizer AdamW): the same op with its `decoupled` operand set -- weight_decay is then torch.optim.AdamW's
+            i = dict(n=e.nparam_padded, step=1, **({'decoupled': 1} if e.optimizer == 'adamw' else {}))
+            opt.add(_lib.OP_ADAM, e.optimizer, p=dict(p, M=_vp(e.M), V=_vp(e.V)), i=i,
                     f=dict(f, beta1=e.betas[0], beta2=e.betas[1], eps=e.eps))
         return opt
 

@@ -333,6 +333,16 @@ IFCBK_API int ifcbk_grad_norm(ifcbk_ctx*, const float* g, int64_t n, float grad_
 IFCBK_API int ifcbk_adam_clip_flat(ifcbk_ctx*, float* p, const float* g, float* m, float* v, float* ema /*nullable*/, int64_t n, float lr,
                     float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale, float ema_w,
                     float max_norm, float* clip_state /*nullable*/, void* stream);
+/* Adam with decoupled weight decay, torch.optim.AdamW's single-tensor step (TRAIN --optimizer AdamW): p[i] <- p[i] * d first, with
+ * d = (float)(1.0 - (double)lr * (double)weight_decay) formed once by this call and used as one fp32 product in the kernel, then
+ * ifcbk_adam_clip_flat's update of m, v and p from the gradient g * grad_scale (* the clip coefficient) WITHOUT a weight_decay * p
+ * term; the weight average is taken from the final p.  Clipping scales the gradient only, never the decay.  The operands, the
+ * nullable ema and clip_state and the IFCBK_EINVAL rules are ifcbk_adam_clip_flat's; in addition weight_decay < 0, infinite or NaN
+ * is IFCBK_EINVAL.  weight_decay == 0 is ifcbk_adam_clip_flat, bit for bit (it is that call).  Every parameter is decayed: leaving
+ * BatchNorm and bias parameters out is the caller's business (slices of the flat buffers).                                         */
+IFCBK_API int ifcbk_adamw_flat(ifcbk_ctx*, float* p, const float* g, float* m, float* v, float* ema /*nullable*/, int64_t n, float lr,
+                    float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale, float ema_w,
+                    float max_norm, float* clip_state /*nullable*/, void* stream);
 IFCBK_API int ifcbk_sgd_clip_flat(ifcbk_ctx*, float* p, const float* g, float* mom, float* ema /*nullable*/, int64_t n, float lr,
                    float momentum, float weight_decay, float grad_scale, float ema_w, float max_norm, float* clip_state /*nullable*/,
                    void* stream);
@@ -580,6 +590,8 @@ enum {
      *   p[4] = E, the weight average's slice (nullable)
      *   p[5] = clip_state (nullable): the op then takes the norm of its G first (ifcbk_grad_norm)
      *   i[0] = n, i[1] = step
+     *   i[2] = decoupled: != 0 hands the same operands to ifcbk_adamw_flat (f[4] is then AdamW's decoupled weight decay, and f[0] the
+     *          rate the decay factor is formed from); 0, what a zeroed op holds, is the L2 form above
      *   f[0] = lr, f[1] = beta1, f[2] = beta2, f[3] = eps, f[4] = weight_decay, f[5] = grad_scale
      *   f[6] = ema_w, read with E
      *   f[7] = max_norm, read with clip_state */
