@@ -157,6 +157,7 @@ _PROTOS = {
     'ifcbk_adam_ema_flat': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _f, _f, _f, _f, _f, _i, _f, _f, _vp]),
     'ifcbk_sgd_ema_flat': (_i, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _f, _f, _f, _f, _f, _vp]),
     'ifcbk_ema_flat': (_i, [_vp, _vp, _vp, C.c_int64, _f, _vp]),
+    'ifcbk_grad_accum_flat': (_i, [_vp, _vp, _vp, C.c_int64, _i, _vp]),
     'ifcbk_grad_clip_state_floats': (_sz, []),
     'ifcbk_grad_norm': (_i, [_vp, _vp, C.c_int64, _f, _f, _vp, _vp]),
     'ifcbk_adam_clip_flat': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _f, _f, _f, _f, _f, _i, _f, _f, _f, _vp, _vp]),

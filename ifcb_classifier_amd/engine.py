@@ -98,7 +98,7 @@ class Engine:
     def __init__(self, net, device=0, max_batch=32, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, dtype='bf16', optimizer='adam',
                  momentum=0.0, plan_only=False, train_batch=None, dp_world=None, class_weights=None, weight_decay=0.0,
                  label_smoothing=0.0, focal_gamma=0.0, mix=False, ema_decay=None, ema_warmup=True, distill=None, clip_grad=None,
-                 blur_radius=None, lr_schedule=None):
+                 blur_radius=None, lr_schedule=None, accumulate=1):
         # dp_world: world size of the data-parallel job this replica belongs to (None: WORLD_SIZE of the launcher, else an
         # initialised torch.distributed group, else 1) -- it picks the program-lane default, and train_step_ddp checks it
         self._dp_world_arg = None if dp_world is None else int(dp_world)
@@ -180,6 +180,14 @@ class Engine:
             raise ValueError('clip_grad must be a finite number > 0, or None for no gradient clipping')
         if self.clip_grad is not None and not 0.0 < C.c_float(self.clip_grad).value < math.inf:
             raise ValueError('clip_grad %r is not a finite fp32 number > 0' % self.clip_grad)
+        # additive (TRAIN --accumulate K): Lightning's accumulate_grad_batches -- the gradients of K consecutive batches are summed into
+        # ``A`` (ifcbk_grad_accum_flat behind every backward) and ONE optimizer step is taken from the sum times 1 / K; BatchNorm and the
+        # step's counters move with every batch.  1: no buffer, and plans, op tables and launches are what they were
+        if isinstance(accumulate, bool) or not isinstance(accumulate, int) or accumulate < 1:
+            raise ValueError('accumulate must be an integer >= 1 (batches per optimizer step), got %r' % (accumulate,))
+        self.accumulate = accumulate
+        self.acc_pending = 0              # batches in the open window (0: closed)
+        self._acc_plan = None             # the plan of the window's last batch: its optimizer program applies the window
         self.net = net
         if dtype not in ('bf16', 'fp32'):
             raise ValueError("dtype must be 'bf16' (performance) or 'fp32' (parity mode)")
@@ -253,6 +261,9 @@ class Engine:
         self.M = torch.zeros(off, dtype=torch.float32, device=dev)
         self.V = torch.zeros(off, dtype=torch.float32, device=dev)
         self.E = torch.zeros(off, dtype=torch.float32, device=dev) if self.ema_decay is not None else None      # layout of P
+        # the accumulator (layout of G): never zeroed, the first batch of a window overwrites it
+        self.A = torch.empty(off, dtype=torch.float32, device=dev) if self.accumulate > 1 else None
+        assert self.A is None or self.A.data_ptr() % 16 == 0
         # the clip state: norm, coefficient, the epoch's two running figures, and the norm kernel's per-block partial sums
         self.clip_state = None
         if self.clip_grad is not None:
@@ -447,6 +458,7 @@ class Engine:
                 bound = 1.0 / math.sqrt(fan_in)
                 v.copy_(((torch.rand(shape, generator=g) * 2 - 1) * bound).to(self.dev))
         self.params_changed()
+        self.accumulate_discard()
 
     def params_changed(self):
         self.packed = False
@@ -932,6 +944,8 @@ class Engine:
             raise RuntimeError('train_step_ddp(world=%d): this engine chose its program lanes for world %d (built before the process '
                                'group existed and without WORLD_SIZE?); pass dp_world=%d to Engine or set IFCBK_LANES'
                                % (int(world), self.dp_world, int(world)))
+        if self.accumulate > 1:
+            return self._acc_step(N, int(world), all_reduce, mark, ddp=True)
         pl = self.plan(N)
         self.ensure_packed(pl)
         self.make_dropout_mask(N)
@@ -1164,7 +1178,8 @@ class Engine:
                                % (N, self.train_batch, self.train_batch, self.train_batch))
         if N > self.window_batch:
             raise RuntimeError('batch %d > %d: the 2 GiB buffer-descriptor window holds %d images of this network per launch, and '
-                               'BatchNorm batch statistics cannot be taken over chunks: use a smaller --batch per GPU (more GPUs)'
+                               'BatchNorm batch statistics cannot be taken over chunks: use a smaller --batch per GPU (more GPUs), or '
+                               'a larger effective batch on the same GPUs with accumulate=K (TRAIN --accumulate K)'
                                % (N, self.window_batch, self.window_batch))
 
     def forward_train(self, N):
@@ -1225,6 +1240,11 @@ class Engine:
     def train_step(self, N, op_ms=None, ev_slot=None, ev_arr=None):
         """one fused launch list: fwd + CE(+0.4 aux) + bwd + Adam + weight repack; loss stays on device."""
         self._check_train_batch(N)
+        if self.accumulate > 1:
+            if op_ms is not None or ev_slot is not None or ev_arr is not None:
+                raise RuntimeError('train_step: per-op timing (op_ms / ev_slot) of an accumulating engine (accumulate=%d) is not supported: '
+                                   'the step is several launch lists; time an engine built with accumulate=1' % self.accumulate)
+            return self._acc_step(N)
         pl = self.plan(N)
         self.ensure_packed(pl)
         self.make_dropout_mask(N)
@@ -1252,3 +1272,73 @@ class Engine:
         # (nbt += 1 and loss_sum += loss are the step's last op: no framework kernel between load_rois and the end of a step)
         self.eval_stats_ready = False
         return pl
+
+    # ------------------------------------------------------------------ gradient accumulation (TRAIN --accumulate)
+    def accumulate_discard(self):
+        """drop an open window without applying it (init_weights, load_state_dict): the next batch opens a new one and overwrites A"""
+        self.acc_pending = 0
+        self._acc_plan = None
+
+    def _acc_add(self, lo, hi, first):
+        """A[lo:hi] = G[lo:hi] (first) or A[lo:hi] + G[lo:hi], behind the backward ops that finished that slice, on their stream; lo is
+        the offset of a parameter tensor, a multiple of 4 elements"""
+        self.ctx.call('ifcbk_grad_accum_flat', _vp(self.A, 4 * lo), _vp(self.G, 4 * lo), hi - lo, 1 if first else 0, self.stream())
+
+    def _acc_step(self, N, world=1, all_reduce=None, mark=None, ddp=False):
+        """one batch of an accumulating engine (train_step; ddp: train_step_ddp): forward, loss and backward at batch N -- the batches of
+        a window may differ in N --, G summed into A, the batch's counters (nbt += 1, loss_sum += loss), and behind the K-th batch of the
+        window its one update.  Data parallel: no collective until the window's last batch, whose backward runs in the bucket segments;
+        each finished slice is accumulated and A's slice exchanged beside the rest of backward"""
+        K = self.accumulate
+        pl = self.plan(N)
+        self.ensure_packed(pl)
+        self.make_dropout_mask(N)
+        self._ema_begin_step(update=False)            # (E = P, ERB = RB as they stand ahead of the window's first forward)
+        first, last = self.acc_pending == 0, self.acc_pending + 1 == K
+        if ddp and last:
+            from .dp import run_overlapped
+
+            def segment(seg):
+                self.run(seg[0])
+                self._acc_add(seg[2], seg[3], first)
+            self.run(pl.fwd_loss)
+            run_overlapped(self.ddp_segments(pl), segment, self.A, all_reduce, mark)
+        else:
+            if self.graph_train and not ddp:
+                self.replay(pl, 'fwd_bwd')
+            else:
+                self.run(pl.fwd_loss)
+                self.run(pl.bwd)
+            self._acc_add(0, self.nparam_padded, first)
+        self.run(pl.acc_count)
+        self.acc_pending += 1
+        self._acc_plan = pl
+        if last:
+            self._acc_apply(1.0 / (K * world))
+        self.eval_stats_ready = False
+        return pl
+
+    def _acc_apply(self, grad_scale):
+        """the window's optimizer step, from A times grad_scale: the step count, the schedule's rate, the weight average, the clip norm
+        (taken over A) and its figures count optimizer steps"""
+        pl = self._acc_plan
+        self.step_count += 1
+        self._ema_begin_step()
+        self._set_update(pl.acc_update.arr[0], grad_scale)
+        self.run(pl.acc_update)                       # (the optimizer over A, then the whole repack)
+        self._ema_end_step()
+        self.accumulate_discard()
+
+    def accumulate_flush(self, world=1, all_reduce=None):
+        """apply an open window that holds fewer than K batches (the end of an epoch), still scaled by 1 / K as Lightning does; nothing
+        on a closed window.  Data parallel (all_reduce given): the whole of A is exchanged in one call ahead of the update.  -> whether
+        an optimizer step was taken"""
+        if self.acc_pending == 0:
+            return False
+        if all_reduce is not None:
+            work = all_reduce(self.A)
+            if work is not None:
+                work.wait()
+        self._acc_apply(1.0 / (self.accumulate * world))
+        self.eval_stats_ready = False
+        return True

@@ -96,6 +96,7 @@ class HipBackbone(nn.Module):
     def _load_from_state_dict(self, *a, **k):
         super()._load_from_state_dict(*a, **k)
         self.engine.params_changed()
+        self.engine.accumulate_discard()
 
     # vgg*_bn: Conv2d(bias=True) -> BatchNorm2d.  The batch mean absorbs the bias, so the engine convolves without it and its
     # running_mean tracks the bias-free conv output; the state_dict shows torchvision's tensor (mean of conv + bias).
@@ -126,6 +127,7 @@ class HipBackbone(nn.Module):
     def load_state_dict(self, state_dict, strict=True):
         r = super().load_state_dict(state_dict, strict)
         self.engine.params_changed()
+        self.engine.accumulate_discard()      # (TRAIN --accumulate: gradients of the weights just replaced)
         return r
 
     def set_dropout_mask(self, mask):
@@ -337,6 +339,13 @@ class NeustonModel(nn.Module):
         if self.blur is not None and self.distill is not None:
             raise ValueError('blur and distill do not combine: the teacher resizes the ROIs itself, at its own input side, and blurring '
                              'its batch alike is not implemented')
+        # additive (TRAIN --accumulate K): Lightning's accumulate_grad_batches -- the engine sums the gradients of K training batches and
+        # takes one optimizer step from the sum times 1 / K; the fit loop flushes a short last window of an epoch.  Absent (older
+        # files) = 1.  The fused path only; RUN ignores it
+        acc = getattr(hparams, 'accumulate', None)
+        if acc is not None and (isinstance(acc, bool) or not isinstance(acc, int) or acc < 1):
+            raise ValueError('accumulate must be an integer >= 1 (batches per optimizer step), got %r' % (acc,))
+        self.accumulate = 1 if acc is None else acc
         self.teacher = None               # a NeustonModel in inference form (attach_teacher)
         self._teacher_ready = False       # the teacher's current input slot holds the student's current batch
         self.model = get_namebrand_model(hparams.MODEL, len(hparams.classes), hparams.pretrained, device, mb,
@@ -348,6 +357,8 @@ class NeustonModel(nn.Module):
                                          **({} if self.ema is None else {'ema_decay': self.ema}),
                                          **({} if self.clip_grad is None else {'clip_grad': self.clip_grad}),
                                          **({} if self.blur is None else {'blur_radius': blur_radius(self.blur)}),
+                                         # (an inference engine -- RUN, a teacher: train_batch=1 -- holds no accumulator)
+                                         **({} if self.accumulate == 1 or train_batch == 1 else {'accumulate': self.accumulate}),
                                          **({} if self.distill is None else {'distill': self.distill}))
         # what upstream would have written at neuston_models.py:55; the engine's fused loss ops compute the same weighted, smoothed mean
         eng = self.model.engine
@@ -373,10 +384,16 @@ class NeustonModel(nn.Module):
         from torch.optim import Adam
         return Adam(self.parameters(), lr=eng.lr, weight_decay=eng.weight_decay)
 
+    def optimizer_steps(self, batches):
+        """TRAIN --accumulate K: the optimizer steps that ``batches`` training batches of one epoch make, ceil(batches / K) -- the short
+        last window of an epoch is applied, so it is a step"""
+        return -(-int(batches) // self.accumulate)
+
     def set_lr_schedule(self, steps_per_epoch):
         """TRAIN --lr-schedule / --warmup / --lr-min: hand the engine the run's schedule, T = emax * steps_per_epoch updates of which
         W = round(warmup * steps_per_epoch) warm up (``steps_per_epoch``: the per-rank length of the training loader, the same on every
-        rank).  Without any of the three flags nothing is set and the engine keeps its one rate.  -> the schedule or None"""
+        rank; with --accumulate K the caller passes ``optimizer_steps`` of that length).  Without any of the three flags nothing is set
+        and the engine keeps its one rate.  -> the schedule or None"""
         from .lr_schedule import LrSchedule, schedule_steps
         hp = self.hparams
         kind = getattr(hp, 'lr_schedule', None) or 'constant'
@@ -622,6 +639,12 @@ class NeustonModel(nn.Module):
         else:
             eng.train_step(N)
         return N
+
+    def fit_flush(self, world=1, all_reduce=None):
+        """TRAIN --accumulate: behind the last training batch of an epoch, apply a window left open with fewer than K batches (scaled by
+        1 / K all the same, as Lightning does).  Every rank holds the same count of batches, so every rank flushes or none does.
+        -> whether an optimizer step was taken"""
+        return self.model.engine.accumulate_flush(world, all_reduce if world > 1 else None)
 
     def eval_current(self, N, with_loss=False):
         eng = self.model.engine

@@ -111,6 +111,23 @@ def _lr_nonneg(text):
     return v
 
 
+def _accumulate(text):
+    try:
+        v = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError('K must be an integer >= 1, got %r' % text) from None
+    if v < 1:
+        raise argparse.ArgumentTypeError('K must be an integer >= 1, got %r' % text)
+    return v
+
+
+def check_accumulate(k, batches_per_epoch):
+    """TRAIN --accumulate K beyond the training batches of an epoch (per GPU) is a usage error: no window would ever fill"""
+    if k > batches_per_epoch:
+        argparse_nn().error('TRAIN --accumulate {} is more than the {} training batch(es) of an epoch: use a K <= {} or a smaller '
+                            '--batch'.format(k, batches_per_epoch, batches_per_epoch))
+
+
 def check_lr_flags(args):
     """the combinations of --lr-schedule / --warmup / --lr-min / --learning-rate / --emax that TRAIN refuses, each with its message"""
     kind, warmup, lr_min = args.lr_schedule, args.warmup, args.lr_min
@@ -290,7 +307,12 @@ class Trainer:
                 n = self._stage(model, rois, ttf, targets, train=True) if n_next is None else n_next
                 model.use_staged()
                 n_next = self._stage(model, nxt[0], ttf, nxt[1], train=True) if nxt is not None else None
+                done = eng.step_count
                 model.fit_current(n, self.world, self._allreduce if self.world > 1 else None)
+                # (TRAIN --accumulate K: the engine steps once per K batches; global_step and the clip report count optimizer steps)
+                global_step += eng.step_count - done
+                epoch_steps += eng.step_count - done
+            if model.fit_flush(self.world, self._allreduce if self.world > 1 else None):       # an epoch's short last window
                 global_step += 1
                 epoch_steps += 1
             model.agg_train_loss = model.epoch_train_loss()
@@ -505,6 +527,7 @@ def do_training(args):
     training_loader = ShardedLoader(training_dataset, args.batch_size, True, args.loaders, rank, world, args.seed)
     print('Loading Validation Dataloader...')
     validation_loader = ShardedLoader(validation_dataset, args.batch_size, False, args.loaders, rank, world, args.seed)
+    check_accumulate(args.accumulate, len(training_loader))
 
     if args.pretrained and not getattr(args, 'weights', None):
         # upstream: pretrained=True downloads torchvision's ImageNet weights (neuston_models.py:23-42).  Training from random
@@ -535,10 +558,17 @@ def do_training(args):
     if eng.window_batch < args.batch_size:
         # --batch is per GPU as upstream (neuston_net.py:102); BatchNorm statistics are per step, so a step cannot be chunked
         raise ValueError('--batch %d: one launch addresses each tensor through a 2 GiB buffer descriptor, which holds %d images '
-                         'of %s; use --batch <= %d per GPU (and more GPUs for a larger global batch)'
+                         'of %s; use --batch <= %d per GPU (and more GPUs for a larger global batch), or --accumulate K for an '
+                         'effective batch of K times --batch on the same GPUs'
                          % (args.batch_size, eng.window_batch, args.MODEL, eng.window_batch))
-    # --lr-schedule / --warmup: the per-rank length of the training loader (--resident: the same length) times --emax is the run
-    sched = classifier.set_lr_schedule(len(training_loader))
+    # --accumulate K: one optimizer step per K training batches, and one more for an epoch's short last window
+    steps_per_epoch = classifier.optimizer_steps(len(training_loader))
+    if args.accumulate > 1:
+        print('Accumulating gradients over {} batches: effective batch {} ({} x {} x {} GPU(s)), {} optimizer steps per epoch'.format(
+            args.accumulate, args.batch_size * args.accumulate * world, args.batch_size, args.accumulate, world, steps_per_epoch))
+    # --lr-schedule / --warmup: the optimizer steps of an epoch -- the per-rank length of the training loader (--resident: the same
+    # length), over --accumulate -- times --emax is the run
+    sched = classifier.set_lr_schedule(steps_per_epoch)
     if sched is not None:
         print('Learning rate: {} schedule over {} steps, {} of them warm-up, from {:g} to {:g}'.format(
             sched.kind, sched.total_steps, sched.warmup_steps, sched.base, sched.base if sched.kind == 'constant' else sched.lr_min))
@@ -800,6 +830,7 @@ def argparse_nn_train(train_subparser):
     optim.add_argument('--focal-gamma', metavar='GAMMA', default=0.0, type=_focal_gamma, action=_ExclusiveLossScalar, help='Focal loss against class imbalance: the loss of an image is scaled by (1 - p)^GAMMA, p the softmax probability of its class, so images the network already classifies confidently count less. A finite float >= 0; composes with --class-norm (its weights are the per-class alpha), not with --label-smoothing; val_loss follows the focal value. Default is 0 (cross-entropy)')
     optim.add_argument('--ema', metavar='DECAY', type=_ema_decay, default=None, help='(MI355X path, additive) Keep an exponential moving average of the weights and of the BatchNorm running statistics, updated inside the fused optimizer step: avg += (1 - d) * (weights - avg) after every step, d = min(DECAY, (1 + t) / (10 + t)) at the t-th step (the warm-up of TensorFlow\'s ExponentialMovingAverage), as torch.optim.swa_utils.get_ema_multi_avg_fn / timm\'s ModelEmaV3. Validation (val_loss, F1, --results files), early stopping, the choice of the best epoch, the saved model and --onnx then use the averaged weights; the training trajectory is unchanged. A float in (0, 1), e.g. 0.999. Default (unset) is no averaging')
     optim.add_argument('--clip-grad', metavar='NORM', type=_clip_grad, default=None, help='(MI355X path, additive) Clip the gradient of every step by its global L2 norm: when the norm over all parameters exceeds NORM the whole gradient is scaled by NORM / (norm + 1e-6), as torch.nn.utils.clip_grad_norm_(parameters, NORM) before every optimizer step / Lightning\'s gradient_clip_val. The norm and the scale are taken on the GPU inside the fused step; weight decay is added to the clipped gradient; with several GPUs the averaged gradient is clipped. Each epoch reports its largest norm and how many steps were clipped. A finite float > 0, e.g. 1.0. Default (unset) is no clipping')
+    optim.add_argument('--accumulate', metavar='K', type=_accumulate, default=1, help='(MI355X path, additive) Gradient accumulation, as Lightning\'s accumulate_grad_batches=K: the gradients of K consecutive training batches are summed on the GPU and one optimizer step is taken from the sum times 1/K, for an effective batch of K x --batch x GPUs where one launch or the card\'s memory holds only --batch. BatchNorm statistics stay per batch; the last window of an epoch is applied even when it holds fewer than K batches, still scaled by 1/K; --lr-schedule, --warmup, --ema, --clip-grad and the step count of the model file count optimizer steps. An integer >= 1 and at most the training batches of an epoch; combines with every other flag. Default is 1 (a step per batch)')
     optim.add_argument('--distill', metavar='TEACHER.ptl', default=None, action=_ExclusiveLossScalar, help='(MI355X path, additive) Knowledge distillation: train MODEL to match the class scores of a trained teacher model file as well as the labels, (1 - A) * CrossEntropy + A * T^2 * KL(softmax(teacher / T) || softmax(student / T)). The teacher may be any backbone and input size (e.g. an inception_v3 teacher for a resnet18 student); its class list must equal the training set\'s. It sees every training batch with the same flips, turns and jitter, resized and normalised as it was trained. Composes with --class-norm (hard term only) and --label-smoothing, not with --focal-gamma, --mixup or --cutmix; val_loss stays the hard loss. RUN needs the student file alone. Default (unset) is no teacher')
     optim.add_argument('--distill-alpha', metavar='A', type=_distill_alpha, default=0.5, help='Weight of the teacher term of --distill, a float in [0, 1]. Default is 0.5')
     optim.add_argument('--distill-temperature', metavar='T', type=_distill_temperature, default=4.0, help='Softmax temperature of --distill, a finite float > 0. Default is 4')

@@ -148,7 +148,7 @@ def _program(*lists):
 
 
 class Plan:
-    """what Engine.plan(N) hands out: thirteen programs, where the optimizer ops sit in ``step`` (step_adam_idxs), the backward list the
+    """what Engine.plan(N) hands out: thirteen programs (an accumulating engine's: two more, acc_update and acc_count), where the optimizer ops sit in ``step`` (step_adam_idxs), the backward list the
     data-parallel step cuts (bwd_list -> ddp_segs), the graphs captured from the programs, the host tables the ops point into (keep)
     and the dispatch switches in force when it was built (dispatch_env, set by Engine.plan)"""
 
@@ -787,10 +787,11 @@ class PlanBuilder:
         evl.add(xent, 'val_loss', p=dict(p, logits=_vp(main.logits)), i=(N, NC), f=dict(f, weight=1.0))
         return lossl, evl, main
 
-    def _optimizer_op(self):
+    def _optimizer_op(self, grad=None):
         e, opt = self.e, OpList()
-        # step, grad_scale and ema_w are stamped per step (Engine._set_update), and with a schedule lr
-        p, f = dict(P=_vp(e.P), G=_vp(e.G)), dict(lr=e.lr, weight_decay=e.weight_decay, grad_scale=1.0)
+        # step, grad_scale and ema_w are stamped per step (Engine._set_update), and with a schedule lr.  grad: the buffer the op reads
+        # its gradient (and, clipping, takes its norm) from -- G, or the accumulator of TRAIN --accumulate
+        p, f = dict(P=_vp(e.P), G=_vp(e.G if grad is None else grad)), dict(lr=e.lr, weight_decay=e.weight_decay, grad_scale=1.0)
         if e.ema_decay is not None:                      # TRAIN --ema: E at the offset of P (every bucket's op carries its slice)
             p['E'] = _vp(e.E)
         if e.clip_grad is not None:                      # TRAIN --clip-grad: the op takes the norm of the whole of G ahead of its update
@@ -831,6 +832,11 @@ class PlanBuilder:
         pl.fwd_loss = _program(fwd_t, lossl)
         pl.fwd_bwd = _program(fwd_t, lossl, bwd)   # the part of a train step whose launch arguments never change: hipGraph-capturable
         pl.adam_pack = _program(opt, pack, cnt)
+        if e.accumulate > 1:
+            # TRAIN --accumulate: every batch runs fwd_loss + bwd (or the fwd_bwd graph), the engine's ifcbk_grad_accum_flat call and the
+            # counters alone; the window's one update reads the accumulator and is followed by the whole repack
+            pl.acc_update = _program(self._optimizer_op(e.A), pack)
+            pl.acc_count = Program(cnt)
         pl.bwd_list = bwd
         pl.keep = self.keep
         return pl

@@ -349,6 +349,14 @@ IFCBK_API int ifcbk_sgd_clip_flat(ifcbk_ctx*, float* p, const float* g, float* m
 /* the plain update e[i] <- e[i] + w * (x[i] - e[i]) over n fp32 elements, for what no optimizer kernel streams (the BatchNorm running
  * statistics).  e and x 16-byte aligned; IFCBK_EINVAL: NULL e or x, n < 0, w outside [0, 1] or NaN.  w == 0 or n == 0 launch nothing. */
 IFCBK_API int ifcbk_ema_flat(ifcbk_ctx*, float* e, const float* x, int64_t n, float w, void* stream);
+/* Gradient accumulation (TRAIN --accumulate): sum the flat gradient g of one batch into the accumulator a, n fp32 elements.
+ * first != 0: a[i] = g[i]; the old bits of a are never read (a NaN left there does not survive: the caller never zeroes a).
+ * first == 0: a[i] = a[i] + g[i], one fp32 add per element -- no FMA, no reassociation, no atomics: the bits of torch's fp32 a + g.
+ * 16-byte accesses over the body, a scalar tail for n % 4; nothing at or behind n is read or written, g is never written; n == 0
+ * launches nothing.  IFCBK_EINVAL (nothing is launched, a keeps its bits): NULL a or g, a or g not 16-byte aligned, n < 0, a == g.
+ * No op kind: the engine calls it between programs (behind backward; per finished bucket in the last data-parallel micro-step), and
+ * the optimizer op of an accumulating engine carries a in its G operand, with grad_scale = 1 / K.                                   */
+IFCBK_API int ifcbk_grad_accum_flat(ifcbk_ctx*, float* a, const float* g, int64_t n, int first, void* stream);
 
 /* ------------------------------------------------------------------ input path
  * replaces PIL convert('RGB') + transforms.Resize([S,S]) (PIL bilinear, antialiased, 8-bit fixed point)
